@@ -5,11 +5,14 @@ bench.py -- imputed subjects/sec on the CAU 5-locus graph (BASELINE.json metric)
 A step = one pass of the grim.impute hot path over one batch of synthetic subjects.  N=1 workload (default):
 BASELINE.json configs[1] -- 10k fully typed synthetic subjects, seed 0.
 
-What is timed (SURVEY 8d protocol), all in one run:
+What is timed (SURVEY 8d protocol):
   value / ms_per_step   HEADLINE: host GL strings in memory -> result records in host memory.  Every step hands the batch's
                         text to the library's streaming pipeline (grim_stream, records mode): tokenizer threads -> pinned
                         staging -> H2D -> kernels -> D2H -> records in pinned host memory, consumed by this process.
                         Steps are pipelined (depth 4) the way a file's chunks are; the graph is resident in HBM.
+                        Exactly --steps steps are timed, in one region (--min-seconds repeats the region).
+A plain run does only that (and --dump-outputs DIR writes the records of the last timed step as .npy files).  --full adds
+the other legs, each measured after the headline:
   kernel_only/roofline  the same batch resident in HBM, kernels only (per-kernel HIP events on the launch stream):
                         the input of the roofline fraction (algorithmic bytes / kernel time / 8 TB/s).
   file_to_file          Imputation.impute_file: subject file on disk -> the six output files on disk (adds the formatter
@@ -35,6 +38,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MAX_CHUNK = 131072
+BLOCK_BYTES = 256 << 20  # the feeder hands the stream whole steps in blocks of at most this size, whatever --steps is
+DUMP_BYTES = 60 << 20  # --dump-outputs: the .npy files stay below 64 MB together
 
 WORKLOADS = {
     # name: (graph, description, default subjects per step on ONE GPU, scaling)
@@ -120,6 +125,30 @@ def make_lines(workload, n, rank, world, rows):
     return synth.SubjectGen(rows, rank).mixed(n)
 
 
+def work_root(work, rank, dist):
+    """The directory the graphs and the benchmark's own files go to: `work` (harness.WORK: $GRIM_WORK, else tests/_work, as
+    for the tests) when the user running the benchmark may write there.  Otherwise (a checkout that is read-only for that
+    user) a fresh directory under the system's temporary directory, the same for every rank, removed when the run ends."""
+    path = [None]
+    if rank == 0:
+        try:
+            os.makedirs(work, exist_ok=True)
+            if os.access(work, os.W_OK | os.X_OK):
+                path[0] = work
+        except OSError:
+            pass
+        if path[0] is None:
+            import atexit
+            import shutil
+            import tempfile
+
+            path[0] = tempfile.mkdtemp(prefix="grim_bench_")
+            atexit.register(shutil.rmtree, path[0], True)
+    if dist is not None:
+        dist.broadcast_object_list(path, src=0)
+    return path[0]
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` outside a torchrun job: run `python -m torch.distributed.run --nproc-per-node N bench.py
     <same arguments>` as a child (one rank per GPU), stdout / stderr inherited so rank 0's JSON line comes through, and exit
@@ -146,6 +175,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="config2", choices=sorted(WORKLOADS) + ["full"])
     ap.add_argument("--subjects", type=int, default=0, help="subjects per step and GPU (default: the workload's size)")
+    ap.add_argument("--full", action="store_true", help="also measure the kernel-only / roofline, file -> file and CPU baseline legs "
+                    "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the result records of the last timed step "
+                    "(rank 0's) as DIR/<name>.npy, float64, at most %d MiB (a fixed sample of the subjects beyond that)" % (DUMP_BYTES >> 20))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--copy-input", action="store_true", help="the stream copies the GL strings it is given (grim_stream_write) instead of reading "
                     "them where they are (grim_stream_write_borrowed: the default here -- the strings are in memory for the whole run)")
@@ -156,12 +189,18 @@ def main():
     ap.add_argument("--chunk-lines", type=int, default=0, help="lines per device batch of the stream (default: the whole step, at most %d)" % MAX_CHUNK)
     ap.add_argument("--depth", type=int, default=8, help="device batches the stream keeps in flight (a step's latency through tokenizer, H2D, kernels, "
                     "D2H and the consumer is several steps long: the depth, not the slowest stage, bounds the rate when it is too small)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="the timed region of --steps steps is repeated until it has run this long in total; "
-                    "ms_per_step is the MEDIAN region (min / max beside it)")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="if > 0, the timed region of --steps steps is repeated (at least 3 times) until it "
+                    "has run this long in total and ms_per_step is the MEDIAN region (min / max beside it); default: one region")
     ap.add_argument("--max-repeats", type=int, default=400)
     ap.add_argument("--sharded", action="store_true", help="time the product's multi-GPU driver instead: grim.shard.impute_sharded, subject file on disk -> "
                     "the six merged output files on disk, chunks pulled from the job's store (a step = one whole file)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.sharded:
+        ap.error("--dump-outputs writes the records of the stream path; --sharded writes its output files itself")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)  # the run changes into the graph's work directory
     if args.workload == "full":
         args.workload = "config2"
     if args.workload == "config5":
@@ -219,6 +258,8 @@ def main():
     chunk_lines = n_step // m
 
     # ---- graph + subjects (host work, outside every timed region) ------------------------------------
+    harness.WORK = work_root(harness.WORK, rank, dist)
+    os.environ["GRIM_WORK"] = harness.WORK  # for the processes it starts (the CPU baseline's workers)
     if gname == "wmda":
         import wmda_scale
         if rank == 0:
@@ -268,36 +309,46 @@ def main():
         return sharded_leg(args, rank, world, dist, work, conf, cfg, graph, lines, gname, desc, n_step, scaling, ranks_seen)
 
     # ---- A. headline: host strings -> host records, K steps through one stream ------------------------
-    # One timed REGION = exactly --steps steps between two barriers.  A region of config 2 lasts a few milliseconds, far too
-    # short to measure on a shared box, so the region is repeated (same stream, pipeline drained in between) until the regions
-    # add up to --min-seconds; the reported step time is the median region's, with the fastest and slowest beside it.
+    # One timed REGION = exactly --steps steps between two barriers.  With --min-seconds the region is repeated (same stream,
+    # pipeline drained in between) until the regions add up to that; the reported step time is then the median region's,
+    # with the fastest and slowest beside it.
     st = nat.Stream(ctx, dgraph, graph.adict, params, ps, cfg["pops"], want_text=False, want_records=True,
                     chunk_lines=chunk_lines, depth=args.depth)
     chunks_per_step = n_step // chunk_lines
     import queue
     cmds = queue.Queue()
     feed_err = []
+    # whole steps per call, in big blocks (the way a file comes in): the library cuts the text into steps of chunk_lines
+    # lines itself, and this thread does not compete for the interpreter with the consumer.  A block holds at most
+    # BLOCK_BYTES, so that the memory of a run does not grow with --steps.  Every block is made here, before anything is timed.
+    block_steps = max(1, min(args.steps, BLOCK_BYTES // len(text)))
+    pieces = {n: text * n for n in {block_steps, args.steps % block_steps, args.warmup % block_steps} if n}
 
     def feed():
         try:
             while True:
-                n = cmds.get()
+                n = cmds.get()  # args.warmup or args.steps
                 if n is None:
                     break
-                # one call per region (the way a file comes in: big blocks): the library cuts the text into steps of
-                # chunk_lines lines itself, and this thread does not compete for the interpreter with the consumer
-                st.write(region_text if n == args.steps else text * n, borrowed=not args.copy_input)
+                q, r = divmod(n, block_steps)
+                for _ in range(q):
+                    st.write(pieces[block_steps], borrowed=not args.copy_input)
+                if r:
+                    st.write(pieces[r], borrowed=not args.copy_input)
             st.finish()
         except Exception as e:  # pragma: no cover
             feed_err.append(e)
 
-    region_text = text * args.steps
     th = threading.Thread(target=feed)
     th.start()
     seen = {"lines": 0, "ok": 0}
+    # --dump-outputs: the chunks of the last timed step.  They are held (not released) until the clock has stopped and are
+    # copied then, unless a step has more chunks than the stream has slots (holding them all would stall it): those are
+    # copied as they come.
+    last_step = []
 
-    def drain(n_chunks):
-        for _ in range(n_chunks):
+    def drain(n_chunks, capture=False):
+        for i in range(n_chunks):
             rec = st.next_records()
             if rec is None:
                 raise RuntimeError("stream ended early: %r" % feed_err)
@@ -307,7 +358,18 @@ def main():
             # per 10 000 records and had become the slowest stage of the pipeline)
             status = res.view(np.uint8).reshape(len(res), nat.RESULT_DT.itemsize)[:, 0]
             seen["ok"] += int(np.count_nonzero((status == nat.ST_OK) & (kinds == nat.K_DEVICE)))
+            if capture and i >= n_chunks - chunks_per_step:
+                if chunks_per_step <= args.depth:
+                    last_step.append(rec)
+                    continue
+                last_step.append(copy_records(rec))
             st.release(handle)
+
+    def release_last_step():
+        for k, rec in enumerate(last_step):
+            if len(rec) == 5:  # held: copy, then hand the chunk back
+                last_step[k] = copy_records(rec)
+                st.release(rec[4])
 
     def agree_max(x):
         if dist is None:
@@ -317,20 +379,27 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
+    capture = bool(args.dump_outputs) and rank == 0
+
     def region():
+        last_step.clear()  # the last region's last step is the one written out
         sync_barrier()
         t0 = time.perf_counter()
         cmds.put(args.steps)
-        drain(args.steps * chunks_per_step)
+        drain(args.steps * chunks_per_step, capture)
         sync_barrier()
-        return agree_max(time.perf_counter() - t0)  # max over ranks
+        dt = agree_max(time.perf_counter() - t0)  # max over ranks
+        release_last_step()
+        return dt
 
     cmds.put(args.warmup)
     drain(args.warmup * chunks_per_step)
     seen.update(lines=0, ok=0)
     regions = [region()]
-    n_ok_per_step = seen["ok"] // max(1, args.steps)
-    repeats = int(min(args.max_repeats, max(3, -(-args.min_seconds // max(regions[0], 1e-9)))))  # the same on every rank
+    n_ok_per_step = seen["ok"] // args.steps
+    repeats = 1
+    if args.min_seconds > 0:
+        repeats = int(min(args.max_repeats, max(3, -(-args.min_seconds // max(regions[0], 1e-9)))))  # the same on every rank
     while len(regions) < repeats:
         regions.append(region())
     cmds.put(None)
@@ -343,7 +412,132 @@ def main():
     regions.sort()
     elapsed = regions[len(regions) // 2]  # the median region: exactly --steps steps
 
-    # ---- B. kernels only: the same batch resident in HBM (roofline input) ----------------------------------
+    if capture:
+        write_outputs(args.dump_outputs, last_step, n_step)
+    # ---- --full: the other legs, after the headline -----------------------------------------------------
+    legs = roofline_leg(args, ctx, dgraph, params, graph, cfg, ps, text, n_step, dflt_n) if args.full else None
+
+    out = None
+    if rank == 0:
+        total_subjects = world * n_step * args.steps  # per region
+        out = {
+            "metric": "imputed subjects/sec (whole node), 5-locus CAU graph",
+            "value": total_subjects / elapsed,
+            "unit": "subjects/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "ms_per_step_min": 1e3 * regions[0] / args.steps, "ms_per_step_max": 1e3 * regions[-1] / args.steps,
+            "repeats": len(regions), "timed_s": sum(regions),
+            "higher_is_better": True,
+            "scaling": scaling,
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": desc + ("; %d subjects per step and GPU, seed=rank" % n_step if scaling == "weak" else
+                                    "; %d subjects per step and GPU" % n_step),
+                "subjects_per_step_per_gpu": n_step, "subjects_with_results_per_step": n_ok_per_step, "ranks": ranks_seen,
+                "graph_nodes": int(graph.arrays["n_nodes"]), "populations": P,
+                "input": "copied by the stream (grim_stream_write)" if args.copy_input else "lent to the stream (grim_stream_write_borrowed): the tokenizer threads read the strings where they lie",
+                "timed_region": "host GL strings in memory -> grim_stream (tokenizer threads, pinned staging, H2D, kernels, D2H) -> "
+                                "result records in pinned host memory, read by the caller; %d device batch(es) of %d lines per step, "
+                                "%d in flight; value = subjects of one region of --steps steps / its time (with --min-seconds: the "
+                                "MEDIAN region time over `repeats` back-to-back regions; barrier + drained pipeline on both sides of "
+                                "each)" % (chunks_per_step, chunk_lines, args.depth),
+                "host_threads": int(os.environ.get("GRIM_HOST_THREADS", "0")) or int(nat.host_lib().grim_default_threads()),
+                "stream_cpu_s": {"tokenize": sstats.tokenize_cpu_s, "device_thread_busy": sstats.device_s},
+                "results_download": (lambda e: "SDMA engine 0x%x named through ROCr (csrc/grim_sdma.h); uploads on the HIP runtime's engine" % e
+                                     if e > 1 else "copy kernel (grim_export_kernel)" if e == 0 else "hipMemcpyAsync")(ctx.export_engine()),
+            },
+        }
+        if legs is not None:
+            out["kernel_only"], out["roofline"] = legs
+        if args.full and world == 1 and not args.no_file:
+            out["file_to_file"] = file_leg(args, work, conf, cfg, imp, lines, rows, n_step)
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_leg(args, work, conf, lines, rows, gname)
+        print(json.dumps(out))
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def copy_records(rec):
+    """one chunk of records (Stream.next_records) -> (first_line, kinds, res, rows), copies.  The rows of every device subject
+    are gathered in a fixed order: by line, then table (T_UMUG .. T_PMUG_POPS), then as the library wrote them.  Where a
+    subject's rows lie in the chunk's row buffer depends on the order in which workgroups took them; what they hold does not."""
+    import ctypes as C
+
+    import numpy as np
+
+    from grim import _native as nat
+
+    first_line, kinds, res, rows_addr, _ = rec
+    kinds, res = kinds.copy(), res.copy()
+    res[kinds != nat.K_DEVICE] = np.zeros(1, dtype=res.dtype)  # only a device subject's record is defined
+    off = res["row_off"].astype(np.int64).ravel()
+    cnt = res["n_rows"].astype(np.int64).ravel()
+    total = int(cnt.sum())
+    rows = np.zeros(0, dtype=nat.ROW_DT)
+    if total:
+        end = int((off + cnt)[cnt > 0].max())
+        view = np.frombuffer((C.c_char * (end * nat.ROW_DT.itemsize)).from_address(rows_addr), dtype=nat.ROW_DT, count=end)
+        rows = view[np.repeat(off - (np.cumsum(cnt) - cnt), cnt) + np.arange(total)]
+    return first_line, kinds, res, rows
+
+
+def write_outputs(out_dir, chunks, n_step):
+    """--dump-outputs: the records of one step (its chunks, copy_records) -> out_dir/<name>.npy, all float64:
+      line [n]          the subject's line in the step's batch
+      kind [n]          K_DEVICE, K_PROBLEM_ID, ... (a line that is not K_DEVICE has zeros below and no rows)
+      codes [n, 4]      status, plan, reason, plan_phased
+      counts [n, 6]     n_pairs, n_genotypes, n_rows of the tables T_UMUG, T_UMUG_POPS, T_PMUG, T_PMUG_POPS
+      max_prob [n]
+      row_hap [R, 4]    haplotype / genotype codes a and b of every row, each as its high and low 32 bits (exact in float64)
+      row_pop [R, 2]    popa, popb
+      row_prob [R]
+    rows in the order of copy_records.  Beyond DUMP_BYTES, a sample of the subjects (a prefix of a permutation of seed 0,
+    in line order) and their rows."""
+    import numpy as np
+
+    line = np.concatenate([c[0] - chunks[0][0] + np.arange(len(c[1])) for c in chunks])
+    kinds = np.concatenate([c[1] for c in chunks])
+    res = np.concatenate([c[2] for c in chunks])
+    rows = np.concatenate([c[3] for c in chunks])
+    assert len(line) == n_step
+    n_rows = res["n_rows"].astype(np.int64).sum(axis=1)
+    cost = 8 * 13 + 8 * 7 * n_rows  # bytes of a subject and its rows in the files below
+    keep = np.ones(len(line), dtype=bool)
+    if cost.sum() > DUMP_BYTES:
+        order = np.random.default_rng(0).permutation(len(line))
+        keep[:] = False
+        keep[order[:int(np.searchsorted(np.cumsum(cost[order]), DUMP_BYTES, side="right"))]] = True
+    rows = rows[np.repeat(keep, n_rows)]
+    res = res[keep]
+    a, b = rows["a"], rows["b"]
+    out = {
+        "line": line[keep], "kind": kinds[keep],
+        "codes": np.stack([res["status"], res["plan"], res["reason"], res["plan_phased"]], axis=1),
+        "counts": np.concatenate([np.stack([res["n_pairs"], res["n_genotypes"]], axis=1), res["n_rows"]], axis=1),
+        "max_prob": res["max_prob"],
+        "row_hap": np.stack([a >> np.uint64(32), a & np.uint64(0xFFFFFFFF), b >> np.uint64(32), b & np.uint64(0xFFFFFFFF)], axis=1),
+        "row_pop": np.stack([rows["popa"], rows["popb"]], axis=1),
+        "row_prob": rows["prob"],
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
+def roofline_leg(args, ctx, dgraph, params, graph, cfg, ps, text, n_step, dflt_n):
+    """--full, leg B: kernels only, the same batch resident in HBM (the roofline's input) -> (kernel_only, roofline)"""
+    import numpy as np
+
+    from grim import _native as nat
+
+    P = len(cfg["pops"])
     parsed = nat.Parsed(graph.adict, text, cfg["planb"])
     subj, toks = parsed.subjects(), parsed.tokens()
     n_tok = int(subj["cnt"].sum())
@@ -395,64 +589,22 @@ def main():
     if prof and whole and prof.get("kernel_only", {}).get("avg_us", {}).get(names[dom]):
         # the roofline fraction recomputed from the COMMITTED kernel-only average: what a reader can check without a GPU
         frac_committed = algo_bytes / (prof["kernel_only"]["avg_us"][names[dom]] * 1e-6) / 1e9 / HBM_PEAK_GBS
-
-    out = None
-    if rank == 0:
-        total_subjects = world * n_step * args.steps  # per region
-        out = {
-            "metric": "imputed subjects/sec (whole node), 5-locus CAU graph",
-            "value": total_subjects / elapsed,
-            "unit": "subjects/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "ms_per_step_min": 1e3 * regions[0] / args.steps, "ms_per_step_max": 1e3 * regions[-1] / args.steps,
-            "repeats": len(regions), "timed_s": sum(regions),
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": desc + ("; %d subjects per step and GPU, seed=rank" % n_step if scaling == "weak" else
-                                    "; %d subjects per step and GPU" % n_step),
-                "subjects_per_step_per_gpu": n_step, "subjects_with_results_per_step": n_ok_per_step, "ranks": ranks_seen,
-                "graph_nodes": int(graph.arrays["n_nodes"]), "populations": P,
-                "input": "copied by the stream (grim_stream_write)" if args.copy_input else "lent to the stream (grim_stream_write_borrowed): the tokenizer threads read the strings where they lie",
-                "timed_region": "host GL strings in memory -> grim_stream (tokenizer threads, pinned staging, H2D, kernels, D2H) -> "
-                                "result records in pinned host memory, read by the caller; %d device batch(es) of %d lines per step, "
-                                "%d in flight; value = subjects of one region of --steps steps / the MEDIAN region time over `repeats` "
-                                "back-to-back regions (barrier + drained pipeline on both sides of each)" % (chunks_per_step, chunk_lines, args.depth),
-                "host_threads": int(os.environ.get("GRIM_HOST_THREADS", "0")) or int(nat.host_lib().grim_default_threads()),
-                "stream_cpu_s": {"tokenize": sstats.tokenize_cpu_s, "device_thread_busy": sstats.device_s},
-                "results_download": (lambda e: "SDMA engine 0x%x named through ROCr (csrc/grim_sdma.h); uploads on the HIP runtime's engine" % e
-                                     if e > 1 else "copy kernel (grim_export_kernel)" if e == 0 else "hipMemcpyAsync")(ctx.export_engine()),
-            },
-            "kernel_only": {
-                "subjects_per_s": len(subj) / (all_ms * 1e-3) if all_ms > 0 else None,
-                "kernel_ms_per_step": all_ms,
-                "synchronous_run_ms": 1e3 * kernel_loop_s / args.kernel_steps,
-                "inputs": "tokenised subjects resident in HBM; results left in HBM (round 1's headline)",
-            },
-            "roofline": {
-                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                "kernel": names[dom] if whole else "+".join(n for n, v in zip(names, per_kernel) if v > 0),
-                "avg_launch_ms": roof_ms, "algorithmic_bytes_per_launch": algo_bytes,
-                "kernel_ms": dict(zip(names, per_kernel)),
-                "frac_from_committed_kernel_only_profile": frac_committed,
-                "rocprof": rocprof,
-            },
-        }
-        if world == 1 and not args.no_file:
-            out["file_to_file"] = file_leg(args, work, conf, cfg, imp, lines, rows, n_step)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_leg(args, work, conf, lines, rows, gname)
-        print(json.dumps(out))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    kernel_only = {
+        "subjects_per_s": len(subj) / (all_ms * 1e-3) if all_ms > 0 else None,
+        "kernel_ms_per_step": all_ms,
+        "synchronous_run_ms": 1e3 * kernel_loop_s / args.kernel_steps,
+        "inputs": "tokenised subjects resident in HBM; results left in HBM (round 1's headline)",
+    }
+    roofline = {
+        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+        "kernel": names[dom] if whole else "+".join(n for n, v in zip(names, per_kernel) if v > 0),
+        "avg_launch_ms": roof_ms, "algorithmic_bytes_per_launch": algo_bytes,
+        "kernel_ms": dict(zip(names, per_kernel)),
+        "frac_from_committed_kernel_only_profile": frac_committed,
+        "rocprof": rocprof,
+    }
+    return kernel_only, roofline
 
 
 def sharded_leg(args, rank, world, dist, work, conf, cfg, graph, lines, gname, desc, n_step, scaling, ranks_seen):

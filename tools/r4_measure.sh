@@ -7,7 +7,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -x -q > $out/gputest.log 2>&1; echo "rc=$?" >> $out/gputest.log
   tail -3 $out/gputest.log
 fi
-B="--steps 5 --warmup 2 --no-file --no-cpu-baseline --min-seconds 0 --kernel-steps 10"
+B="--full --steps 5 --warmup 2 --no-file --no-cpu-baseline --min-seconds 0 --kernel-steps 10"
 GRIM_DEBUG_CLASSES=1 timeout -k 10 300 python bench.py --workload config4 $B > $out/c4.json 2> $out/c4.err; echo "c4 rc=$?"
 GRIM_NO_MID=1 timeout -k 10 300 python bench.py --workload config4 $B > $out/c4_nomid.json 2> $out/c4_nomid.err; echo "c4 nomid rc=$?"
 python - <<PY
