@@ -43,7 +43,7 @@ typedef struct grim_batch grim_batch;
 grim_ctx *grim_create(int device_id);
 void grim_destroy(grim_ctx *ctx);
 const char *grim_last_error(grim_ctx *ctx);
-/* 1 if a HIP device is usable by this process, 0 otherwise (never raises). */
+/* number of HIP devices this process can use, 0 when there is none or the runtime fails (never raises). */
 int grim_device_count(void);
 /* How a stream's results come from HBM to pinned host memory on this context: the bit of the SDMA engine the downloads are
  * pinned to (hsa_amd_sdma_engine_id_t, > 1: csrc/grim_sdma.h -- uploads stay on engine 0x1, so both directions of the link
@@ -215,8 +215,8 @@ int grim_batch_run_repeat(grim_batch *b, uint32_t n);
 int grim_batch_set_timing(grim_batch *b, int on);
 /* device time of the last grim_batch_run in timing mode (0 otherwise):
  * which = 0 all kernels, 1 half-wave + one-wave + general kernel, 2 plan-B/C kernel, 3 half-wave kernel, 4 general plan-A
- *         kernel, 5 one-wave kernel, 6 the table kernels, 7 the half-wave kernel's row compaction (each from the kernels' own
- *         start/stop events);
+ *         kernel, 5 one-wave kernel, 6 the table kernels, 7 the half-wave kernel's row compaction, 8 the device tokenizer,
+ *         9 the mid-size kernel (each from the kernels' own start/stop events; 0 = 1 + 2 + 6 + 7 + 8);
  * which | 0x10 = the mean of that figure over all runs since timing was switched on */
 double grim_batch_kernel_ms(const grim_batch *b, int which);
 /* algorithmic byte counters of the last run: [0] probes, [1] CSR neighbour ids,
@@ -405,6 +405,43 @@ typedef struct {
 int grim_stream_next_records(grim_stream *s, grim_stream_records *out);
 int grim_stream_release_records(grim_stream *s, grim_stream_records *rec);
 void grim_stream_free(grim_stream *s);
+
+/* ======================= M-step of an EM iteration: haplotype / population counts (csrc/grim_em.h) ====================
+ * The reference has no counterpart: its sibling EM package folds the rows write_best_hap_race_pairs prints
+ * (impute.py:79-99, 2079-2088) on the host.  Here the fold runs on the rows a finished batch holds in HBM.
+ * Per subject with status GRIM_ST_OK whose phased rows did not come from Plan C, rows k = 0.. in rank order with
+ * probabilities p_k: total = ((p_0 + p_1) + p_2) + ..., w_k = p_k / total; (haplotype a_k, population popa_k) += w_k,
+ * then (b_k, popb_k) += w_k.  Every counter is the left-to-right fp64 sum of its contributions in (subject, rank, side)
+ * order over all batches in the order they were accumulated: bit for bit the same however the input was cut.
+ * A haplotype is its alleles: bit GRIM_KEY_GRAPH_ORDER of a row's key is dropped.
+ * n_alleles[slot] = grim_dict_count(slot) when the batches were tokenised: a haplotype that holds an allele id at or above
+ * it (an allele private to its subject) is not counted on the device; its contributions come back as spill records, in
+ * contract order, for the host to fold by allele text (grim_parsed_allele).
+ * first_capacity: haplotype slots to begin with (rounded up to a power of two, at least 64); the table doubles on demand. */
+typedef struct grim_em grim_em;
+typedef struct {
+  uint64_t key;   /* haplotype key, GRIM_KEY_GRAPH_ORDER cleared */
+  double w;
+  uint32_t batch; /* ordinal of the grim_em_accumulate call, from 0 */
+  uint32_t subject, row; /* subject index inside that batch, rank of the row */
+  uint16_t pop, side;    /* side 0 = a, 1 = b */
+} grim_em_spill_rec; /* 32 bytes */
+grim_em *grim_em_create(grim_ctx *ctx, const uint32_t n_alleles[GRIM_MAXL], uint32_t n_pops, uint64_t first_capacity);
+/* after grim_batch_run, on a batch whose params have em_mr and out_haps and whose graph has n_pops populations (else -3
+ * and a grim_last_error text, nothing launched); synchronous; reads the batch's device arrays, copies no result down */
+int grim_em_accumulate(grim_em *em, grim_batch *b);
+uint64_t grim_em_entries(const grim_em *em); /* (haplotype, population) counters that were added to */
+/* keys / pops / counts [grim_em_entries], in (key, population) order */
+int grim_em_export(grim_em *em, uint64_t *keys, uint32_t *pops, double *counts);
+uint64_t grim_em_spill_count(const grim_em *em);
+int grim_em_spill(grim_em *em, uint64_t first, uint64_t n, grim_em_spill_rec *out);
+/* [0] subjects used [1] subjects skipped because their phased rows came from Plan C [2] contributions [3] rehashes */
+int grim_em_stats(const grim_em *em, uint64_t out[4]);
+/* subjects with status GRIM_ST_UNSUPPORTED in the batch of the last grim_em_accumulate (the caller reports them) */
+uint64_t grim_em_last_unsupported(const grim_em *em);
+/* device time of the last grim_em_accumulate: its kernels between their own start/stop events */
+double grim_em_kernel_ms(const grim_em *em);
+void grim_em_free(grim_em *em);
 
 #ifdef __cplusplus
 }

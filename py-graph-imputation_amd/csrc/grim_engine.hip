@@ -21,6 +21,7 @@
 #include "grim_mid.h"
 #include "grim_tables.h"
 #include "grim_tokdev.h"
+#include "grim_em.h"
 #include "grim_engine_internal.h"
 #include "grim_host_internal.h"
 #include "grim_sdma.h"
@@ -354,6 +355,7 @@ struct grim_batch {
   double acc_ms[10];  // sums over the timed runs since timing was switched on (index = `which`)
   uint32_t n_timed;
   uint32_t rows_used;
+  bool ran_ok = false;  // the last grim_batch_run finished and nothing was loaded since: res / rows hold its results (grim_em_accumulate)
   unsigned long long counters[8];
 };
 
@@ -1004,6 +1006,7 @@ int engine_batch_load(grim_batch *b, const EngineLoad *ld) {
   grim_ctx *c = b->ctx;
   use_device(c->device);
   DevArgs &A = b->a;
+  b->ran_ok = false;
   if (ld->n_subj > b->plan.n_subj || ld->tok_used > b->plan.tok_cap) {
     set_err(c, "engine_batch_load: beyond what the batch was planned for");
     return -1;
@@ -1450,6 +1453,7 @@ int engine_batch_wait(grim_batch *b) {
     return -1;
   }
   b->enqueued = false;
+  b->ran_ok = false;
   HIPCHK(hipEventSynchronize(b->ev_done), c, -1);
   if (b->timing) {
     if (b->n_small || b->n_dev_lines) HIPCHK(hipEventElapsedTime(&b->ms_s, b->ev[3], b->ev[5]), c, -1);
@@ -1532,6 +1536,7 @@ int engine_batch_wait(grim_batch *b) {
     set_err(c, "grim_batch_run: output row pool exhausted (raise GRIM_ROW_CAP or lower the batch size)");
     return -2;
   }
+  b->ran_ok = true;
   return 0;
 }
 
@@ -1751,4 +1756,320 @@ static void batch_destroy(grim_batch *b) {
   for (void *p : pin)
     if (p) hipHostFree(p);
   delete b;
+}
+
+// =================================================================================================
+// M-step accumulator (grim_em.h): haplotype / population counts from the phased rows of finished batches
+// =================================================================================================
+static_assert(sizeof(EmSpill) == sizeof(grim_em_spill_rec) && sizeof(EmSpill) == 32, "spill record layout");
+
+struct grim_em {
+  grim_ctx *ctx;
+  EmLimits lim;
+  EmTable T;               // keys / popmask / counts in HBM
+  uint64_t cap;            // slots (a power of two); at most half of them are ever used
+  unsigned long long *d_stat;
+  // per-batch buffers, kept and grown: positions per subject, (group, position) ping-pong, weights, radix counts, spill
+  uint32_t *d_first, *d_grp[2], *d_idx[2], *d_cnt;
+  double *d_w, *d_ws;
+  EmSpill *d_spill;
+  uint64_t first_cap, contrib_cap, cnt_cap;
+  std::vector<EmSpill> spill;  // every batch's records, in contract order
+  uint64_t table_used, entries, n_used, n_planc, n_contrib, n_rehash, last_unsupported;
+  uint32_t batch_no;
+  hipEvent_t ev[6];
+  double last_ms;
+};
+
+static void em_table_free(EmTable &T) {
+  if (T.keys) hipFree(T.keys);
+  if (T.popmask) hipFree(T.popmask);
+  if (T.counts) hipFree(T.counts);
+  T.keys = T.popmask = nullptr;
+  T.counts = nullptr;
+}
+
+static bool em_table_alloc(grim_ctx *c, EmTable &T, uint64_t cap, uint32_t P) {
+  T.keys = T.popmask = nullptr;
+  T.counts = nullptr;
+  T.mask = (uint32_t)(cap - 1);
+  T.P = P;
+  if (hipMalloc((void **)&T.keys, 8 * cap) != hipSuccess || hipMalloc((void **)&T.popmask, 8 * cap) != hipSuccess ||
+      hipMalloc((void **)&T.counts, 8 * cap * P) != hipSuccess || hipMemsetAsync(T.keys, 0, 8 * cap, c->stream) != hipSuccess ||
+      hipMemsetAsync(T.popmask, 0, 8 * cap, c->stream) != hipSuccess || hipMemsetAsync(T.counts, 0, 8 * cap * P, c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    em_table_free(T);
+    return false;
+  }
+  return true;
+}
+
+extern "C" grim_em *grim_em_create(grim_ctx *c, const uint32_t n_alleles[GRIM_MAXL], uint32_t n_pops, uint64_t first_capacity) {
+  if (!c || !n_alleles || n_pops == 0 || n_pops > GRIM_MAXPOP) {
+    set_err(c, "grim_em_create: bad arguments");
+    return nullptr;
+  }
+  use_device(c->device);
+  uint64_t cap = 64;
+  while (cap < first_capacity) cap *= 2;
+  if (cap * n_pops > (1ull << 31)) {
+    set_err(c, "grim_em_create: first_capacity times the populations is beyond 2^31 counters");
+    return nullptr;
+  }
+  grim_em *e = new grim_em();
+  e->ctx = c;
+  for (int q = 0; q < GRIM_MAXL; ++q) e->lim.n_alleles[q] = n_alleles[q];
+  e->cap = cap;
+  bool ok = em_table_alloc(c, e->T, cap, n_pops);
+  ok = ok && hipMalloc((void **)&e->d_stat, 8 * EM_S_COUNT) == hipSuccess && hipMemsetAsync(e->d_stat, 0, 8 * EM_S_COUNT, c->stream) == hipSuccess;
+  for (int k = 0; ok && k < 6; ++k) ok = hipEventCreate(&e->ev[k]) == hipSuccess;
+  ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    set_err(c, "grim_em_create: device allocation failed");
+    grim_em_free(e);
+    return nullptr;
+  }
+  return e;
+}
+
+extern "C" void grim_em_free(grim_em *e) {
+  if (!e) return;
+  use_device(e->ctx->device);
+  hipStreamSynchronize(e->ctx->stream);
+  em_table_free(e->T);
+  void *dev[] = {e->d_stat, e->d_first, e->d_grp[0], e->d_grp[1], e->d_idx[0], e->d_idx[1], e->d_cnt, e->d_w, e->d_ws, e->d_spill};
+  for (void *p : dev)
+    if (p) hipFree(p);
+  for (int k = 0; k < 6; ++k)
+    if (e->ev[k]) hipEventDestroy(e->ev[k]);
+  delete e;
+}
+
+template <typename T>
+static bool em_grow(T *&ptr, uint64_t n) {
+  if (ptr) hipFree(ptr);
+  ptr = nullptr;
+  if (hipMalloc((void **)&ptr, sizeof(T) * n) != hipSuccess) {
+    (void)hipGetLastError();
+    ptr = nullptr;
+    return false;
+  }
+  return true;
+}
+
+// a table twice the size, the entries moved by a kernel with their counters; returns the kernel's milliseconds or < 0
+static double em_rehash(grim_em *e) {
+  grim_ctx *c = e->ctx;
+  if (e->cap * 2 * e->T.P > (1ull << 31)) {
+    set_err(c, "grim_em_accumulate: the table cannot grow beyond 2^31 counters");
+    return -1.0;
+  }
+  EmTable to;
+  if (!em_table_alloc(c, to, e->cap * 2, e->T.P)) {
+    set_err(c, "grim_em_accumulate: device allocation failed (rehash)");
+    return -1.0;
+  }
+  float ms = 0;
+  bool ok = hipEventRecord(e->ev[4], c->stream) == hipSuccess;
+  hipLaunchKernelGGL(em_rehash_kernel, dim3((uint32_t)((e->cap + 255) / 256)), dim3(256), 0, c->stream, e->T, to, e->d_stat);
+  ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(e->ev[5], c->stream) == hipSuccess &&
+       hipStreamSynchronize(c->stream) == hipSuccess && hipEventElapsedTime(&ms, e->ev[4], e->ev[5]) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    em_table_free(to);
+    set_err(c, "grim_em_accumulate: rehash failed");
+    return -1.0;
+  }
+  em_table_free(e->T);
+  e->T = to;
+  e->cap *= 2;
+  e->n_rehash++;
+  return ms;
+}
+
+extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
+  if (!e || !b) return -1;
+  grim_ctx *c = e->ctx;
+  e->last_ms = 0.0;
+  e->last_unsupported = 0;
+  if (b->ctx != c) {
+    set_err(c, "grim_em_accumulate: the batch belongs to another context");
+    return -3;
+  }
+  if (!b->a.prm.em_mr || !b->a.prm.out_haps) {
+    set_err(c, "grim_em_accumulate: the batch was built without em_mr / out_haps: its phased rows carry no populations");
+    return -3;
+  }
+  if (!b->ran_ok) {
+    set_err(c, "grim_em_accumulate: the batch holds no finished run (call grim_batch_run first)");
+    return -3;
+  }
+  if (b->g->d.P != e->T.P) {
+    set_err(c, "grim_em_accumulate: the batch's graph has another number of populations");
+    return -3;
+  }
+  use_device(c->device);
+  hipStream_t st = c->stream;
+  const uint32_t n = b->n_subj;
+  const uint32_t batch_no = e->batch_no++;
+  if (n == 0) return 0;
+  if ((uint64_t)n + 1 > e->first_cap) {
+    if (!em_grow(e->d_first, (uint64_t)n + 1)) {
+      e->first_cap = 0;
+      set_err(c, "grim_em_accumulate: device allocation failed");
+      return -1;
+    }
+    e->first_cap = (uint64_t)n + 1;
+  }
+  // ---- rows per subject -> positions ------------------------------------------------------------------------------
+  HIPCHK(hipMemsetAsync(e->d_stat, 0, 8 * 4, st), c, -1);  // the per-call words
+  HIPCHK(hipMemsetAsync(e->d_stat + EM_S_FAULT, 0, 8, st), c, -1);
+  HIPCHK(hipEventRecord(e->ev[0], st), c, -1);
+  hipLaunchKernelGGL(em_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, b->a.res, n, b->rows_used, e->d_first, e->d_stat);
+  hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, e->d_first, n);
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(e->ev[1], st), c, -1);
+  uint32_t n_rows = 0;
+  HIPCHK(hipMemcpyAsync(&n_rows, e->d_first + n, 4, hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]), c, -1);
+  double total_ms = ms;
+  if (n_rows > b->rows_used || n_rows > 0x3FFFFFFFu) {
+    set_err(c, "grim_em_accumulate: more phased rows than the batch holds");
+    return -1;
+  }
+  const uint32_t C = 2 * n_rows;  // contributions
+  if (C) {
+    // ---- room first: C contributions insert at most C haplotypes -----------------------------------------------------
+    while (e->table_used + C > e->cap / 2) {
+      const double r = em_rehash(e);
+      if (r < 0) return -1;
+      total_ms += r;
+    }
+    if (C > e->contrib_cap) {
+      const uint64_t want = (uint64_t)C + C / 4;
+      e->contrib_cap = 0;
+      if (!em_grow(e->d_grp[0], want) || !em_grow(e->d_grp[1], want) || !em_grow(e->d_idx[0], want) || !em_grow(e->d_idx[1], want) ||
+          !em_grow(e->d_w, want) || !em_grow(e->d_ws, want) || !em_grow(e->d_spill, want)) {
+        set_err(c, "grim_em_accumulate: device allocation failed");
+        return -1;
+      }
+      e->contrib_cap = want;
+    }
+    const uint32_t n_chunks = (C + GRIM_EM_CHUNK - 1) / GRIM_EM_CHUNK;
+    if (256ull * n_chunks + 1 > e->cnt_cap) {
+      e->cnt_cap = 0;
+      if (!em_grow(e->d_cnt, 256ull * n_chunks + 1)) {
+        set_err(c, "grim_em_accumulate: device allocation failed");
+        return -1;
+      }
+      e->cnt_cap = 256ull * n_chunks + 1;
+    }
+    HIPCHK(hipEventRecord(e->ev[2], st), c, -1);
+    hipLaunchKernelGGL(em_weight_kernel, dim3((n + 3) / 4), dim3(256), 0, st, b->a.res, b->a.rows, n, e->d_first, e->T, e->lim, batch_no,
+                       e->d_grp[0], e->d_idx[0], e->d_w, e->d_spill, C, e->d_stat);
+    // groups are < cap * P; one bit more sends the records without a group behind them
+    uint32_t bits = 1;
+    while ((1ull << bits) < e->cap * e->T.P) ++bits;
+    int cur = 0;
+    for (uint32_t shift = 0; shift < bits + 1; shift += 8) {
+      hipLaunchKernelGGL(em_radix_hist_kernel, dim3(n_chunks), dim3(64), 0, st, e->d_grp[cur], C, n_chunks, shift, e->d_cnt);
+      hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, e->d_cnt, 256u * n_chunks);
+      hipLaunchKernelGGL(em_radix_scatter_kernel, dim3(n_chunks), dim3(64), 0, st, e->d_grp[cur], e->d_idx[cur], e->d_grp[cur ^ 1],
+                         e->d_idx[cur ^ 1], C, n_chunks, shift, e->d_cnt);
+      cur ^= 1;
+    }
+    hipLaunchKernelGGL(em_gather_kernel, dim3((C + 255) / 256), dim3(256), 0, st, e->d_idx[cur], e->d_w, e->d_ws, C);
+    hipLaunchKernelGGL(em_sum_kernel, dim3((C + 255) / 256), dim3(256), 0, st, e->d_grp[cur], e->d_ws, C, e->T, e->d_stat);
+    HIPCHK(hipGetLastError(), c, -1);
+    HIPCHK(hipEventRecord(e->ev[3], st), c, -1);
+  }
+  unsigned long long h[EM_S_COUNT];
+  HIPCHK(hipMemcpyAsync(h, e->d_stat, sizeof(h), hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  if (C) {
+    HIPCHK(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]), c, -1);
+    total_ms += ms;
+  }
+  e->last_ms = total_ms;
+  e->last_unsupported = h[EM_S_UNSUPPORTED];
+  if (h[EM_S_FAULT] || h[EM_S_SPILL] > C) {
+    set_err(c, "grim_em_accumulate: the haplotype table overflowed (internal)");
+    return -1;
+  }
+  e->table_used = h[EM_S_TABLE];
+  e->entries = h[EM_S_ENTRIES];
+  e->n_used += h[EM_S_USED];
+  e->n_planc += h[EM_S_PLANC];
+  e->n_contrib += C;
+  if (h[EM_S_SPILL]) {
+    const size_t at = e->spill.size(), ns = (size_t)h[EM_S_SPILL];
+    e->spill.resize(at + ns);
+    HIPCHK(hipMemcpy(e->spill.data() + at, e->d_spill, sizeof(EmSpill) * ns, hipMemcpyDeviceToHost), c, -1);
+    std::sort(e->spill.begin() + at, e->spill.end(), [](const EmSpill &x, const EmSpill &y) {
+      if (x.subject != y.subject) return x.subject < y.subject;
+      if (x.row != y.row) return x.row < y.row;
+      return x.side < y.side;
+    });
+  }
+  return 0;
+}
+
+extern "C" uint64_t grim_em_entries(const grim_em *e) { return e ? e->entries : 0; }
+extern "C" uint64_t grim_em_spill_count(const grim_em *e) { return e ? e->spill.size() : 0; }
+extern "C" uint64_t grim_em_last_unsupported(const grim_em *e) { return e ? e->last_unsupported : 0; }
+extern "C" double grim_em_kernel_ms(const grim_em *e) { return e ? e->last_ms : 0.0; }
+
+extern "C" int grim_em_spill(grim_em *e, uint64_t first, uint64_t n, grim_em_spill_rec *out) {
+  if (!e || !out || first > e->spill.size() || n > e->spill.size() - first) return -1;
+  if (n) memcpy(out, e->spill.data() + first, sizeof(EmSpill) * (size_t)n);
+  return 0;
+}
+
+extern "C" int grim_em_stats(const grim_em *e, uint64_t out[4]) {
+  if (!e || !out) return -1;
+  out[0] = e->n_used;
+  out[1] = e->n_planc;
+  out[2] = e->n_contrib;
+  out[3] = e->n_rehash;
+  return 0;
+}
+
+extern "C" int grim_em_export(grim_em *e, uint64_t *keys, uint32_t *pops, double *counts) {
+  if (!e) return -1;
+  if (e->entries == 0) return 0;
+  if (!keys || !pops || !counts) return -1;
+  grim_ctx *c = e->ctx;
+  use_device(c->device);
+  const uint32_t P = e->T.P;
+  std::vector<unsigned long long> hk(e->cap), hm(e->cap);
+  std::vector<double> hc(e->cap * P);
+  HIPCHK(hipMemcpy(hk.data(), e->T.keys, 8 * e->cap, hipMemcpyDeviceToHost), c, -1);
+  HIPCHK(hipMemcpy(hm.data(), e->T.popmask, 8 * e->cap, hipMemcpyDeviceToHost), c, -1);
+  HIPCHK(hipMemcpy(hc.data(), e->T.counts, 8 * e->cap * P, hipMemcpyDeviceToHost), c, -1);
+  // slot numbers depend on which insert came first: the entries leave in (key, population) order
+  std::vector<std::pair<uint64_t, uint64_t>> order;  // (key, slot)
+  for (uint64_t s = 0; s < e->cap; ++s)
+    if (hk[s] && hm[s]) order.emplace_back(hk[s] & ~GRIM_VALID, s);
+  std::sort(order.begin(), order.end());
+  uint64_t k = 0;
+  for (const auto &o : order)
+    for (uint32_t p = 0; p < P; ++p)
+      if ((hm[o.second] >> p) & 1ull) {
+        if (k >= e->entries) {
+          set_err(c, "grim_em_export: more entries than counted (internal)");
+          return -1;
+        }
+        keys[k] = o.first;
+        pops[k] = p;
+        counts[k] = hc[o.second * P + p];
+        ++k;
+      }
+  if (k != e->entries) {
+    set_err(c, "grim_em_export: fewer entries than counted (internal)");
+    return -1;
+  }
+  return 0;
 }

@@ -300,6 +300,110 @@ class DeviceBatch:
             pass
 
 
+# ---- M-step accumulator (grim_em_*): haplotype / population counts from the phased rows of finished batches ----
+EXPORTS += [
+    "grim_em_create", "grim_em_accumulate", "grim_em_entries", "grim_em_export", "grim_em_spill_count", "grim_em_spill",
+    "grim_em_stats", "grim_em_last_unsupported", "grim_em_kernel_ms", "grim_em_free",
+]
+
+SPILL_DT = np.dtype([("key", "<u8"), ("w", "<f8"), ("batch", "<u4"), ("subject", "<u4"), ("row", "<u4"), ("pop", "<u2"), ("side", "<u2")])
+assert SPILL_DT.itemsize == 32
+
+_em_ready = False
+
+
+def _em_lib():
+    global _em_ready
+    L = lib()
+    if not _em_ready:
+        L.grim_em_create.restype = C.c_void_p
+        L.grim_em_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64]
+        L.grim_em_accumulate.restype = C.c_int
+        L.grim_em_accumulate.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_em_entries.restype = C.c_uint64
+        L.grim_em_entries.argtypes = [C.c_void_p]
+        L.grim_em_export.restype = C.c_int
+        L.grim_em_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_em_spill_count.restype = C.c_uint64
+        L.grim_em_spill_count.argtypes = [C.c_void_p]
+        L.grim_em_spill.restype = C.c_int
+        L.grim_em_spill.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
+        L.grim_em_stats.restype = C.c_int
+        L.grim_em_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.grim_em_last_unsupported.restype = C.c_uint64
+        L.grim_em_last_unsupported.argtypes = [C.c_void_p]
+        L.grim_em_kernel_ms.restype = C.c_double
+        L.grim_em_kernel_ms.argtypes = [C.c_void_p]
+        L.grim_em_free.argtypes = [C.c_void_p]
+        _em_ready = True
+    return L
+
+
+class EmAccumulator:
+    """grim_em: per-population haplotype counts summed on the device from the phased rows of finished batches, in input
+    order and bit for bit independent of the batch cuts (include/grim_hip.h, the grim_em_* block)."""
+
+    def __init__(self, ctx, n_alleles, n_pops, first_capacity=1 << 20):
+        L = _em_lib()
+        self.ctx = ctx
+        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
+        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        self.h = L.grim_em_create(ctx.h, arr, int(n_pops), int(first_capacity))
+        if not self.h:
+            raise NativeError("grim_em_create failed: " + ctx.error())
+
+    def accumulate(self, batch):
+        """the counts of one DeviceBatch after its run(); synchronous"""
+        rc = _em_lib().grim_em_accumulate(self.h, batch.h)
+        if rc != 0:
+            raise NativeError("grim_em_accumulate failed (%d): %s" % (rc, self.ctx.error()))
+
+    def entries(self):
+        return int(_em_lib().grim_em_entries(self.h))
+
+    def export(self):
+        """-> (keys u64, pops u32, counts f64), one element per (haplotype, population) counter, in (key, population) order"""
+        n = self.entries()
+        keys, pops, counts = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64)
+        if n and _em_lib().grim_em_export(self.h, _ptr(keys), _ptr(pops), _ptr(counts)) != 0:
+            raise NativeError("grim_em_export failed: " + self.ctx.error())
+        return keys, pops, counts
+
+    def spill_count(self):
+        return int(_em_lib().grim_em_spill_count(self.h))
+
+    def spill(self, first=0, n=None):
+        """spill records [first, first + n): contributions of haplotypes that hold an allele private to their subject"""
+        if n is None:
+            n = self.spill_count() - first
+        out = np.zeros(max(int(n), 0), dtype=SPILL_DT)
+        if n > 0 and _em_lib().grim_em_spill(self.h, int(first), int(n), _ptr(out)) != 0:
+            raise NativeError("grim_em_spill: range outside the list")
+        return out
+
+    def stats(self):
+        out = (C.c_uint64 * 4)()
+        _em_lib().grim_em_stats(self.h, out)
+        return {"subjects_used": int(out[0]), "skipped_plan_c": int(out[1]), "contributions": int(out[2]), "rehashes": int(out[3])}
+
+    def last_unsupported(self):
+        return int(_em_lib().grim_em_last_unsupported(self.h))
+
+    def kernel_ms(self):
+        return float(_em_lib().grim_em_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            _em_lib().grim_em_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ======================================================================================================
 # host-side helpers of the library (C++: allele dictionary, tokenizer, formatter) -- no GPU needed
 # ======================================================================================================

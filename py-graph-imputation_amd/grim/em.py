@@ -1,0 +1,205 @@
+"""
+The M-step of an EM iteration over the imputation: per-population haplotype counts from the phased `hap;pop` rows.
+
+The reference has no M-step of its own -- its sibling EM package folds the rows `write_best_hap_race_pairs` prints
+(impute.py:79-99, 2079-2088).  The operation is defined here:
+
+    for every subject, in input-line order, with phased rows k = 0..n-1 in rank order and probabilities p_k
+        (a subject whose phased rows came from Plan C -- populations `all_pops` -- is skipped and counted):
+      total = ((p_0 + p_1) + p_2) + ...
+      w_k   = p_k / total
+      count[pop a_k][hap a_k] += w_k, then count[pop b_k][hap b_k] += w_k          for k = 0, 1, ...
+
+Every counter is the left-to-right fp64 sum of its contributions in (line, rank, side) order.
+
+`m_step_counts` runs it on the device, on the rows a batch leaves in HBM (csrc/grim_em.h): no text is formatted, no row
+is copied to the host.  `fold_pmug_text` is the same fold over `.pmug` text in plain Python floats.  The two agree bit for
+bit.  There is no CPU fallback of `m_step_counts`.
+"""
+
+import gzip
+import os
+
+import numpy as np
+
+from . import _native as nat
+
+ALL_POPS = "all_pops"
+
+
+def fold_pmug_text(text):
+    """`.pmug` text in `id,hap;pop,hap;pop,p,rank` form -> ({pop: {haplotype: count}}, stats).  A subject is the run of rows
+    from one rank 0 to the next; a subject with an `all_pops` row is skipped (stats["skipped_plan_c"])."""
+    counts = {}
+    stats = {"subjects_used": 0, "skipped_plan_c": 0, "contributions": 0}
+
+    def flush(rows):
+        if not rows:
+            return
+        if any(pa == ALL_POPS or pb == ALL_POPS for _, pa, _, pb, _ in rows):
+            stats["skipped_plan_c"] += 1
+            return
+        total = rows[0][4]
+        for r in rows[1:]:
+            total = total + r[4]
+        if not total > 0.0:
+            raise ValueError("phased rows whose probabilities add up to %r" % total)
+        for ha, pa, hb, pb, p in rows:
+            w = p / total
+            for hap, pop in ((ha, pa), (hb, pb)):
+                d = counts.setdefault(pop, {})
+                d[hap] = d[hap] + w if hap in d else w
+        stats["subjects_used"] += 1
+        stats["contributions"] += 2 * len(rows)
+
+    rows, sid = [], None
+    for line in text.splitlines():
+        if not line:
+            continue
+        f = line.split(",")
+        if len(f) != 5 or ";" not in f[1] or ";" not in f[2]:
+            raise ValueError("not a hap;pop,hap;pop row: %r" % line)
+        if int(f[4]) == 0 or f[0] != sid:
+            flush(rows)
+            rows, sid = [], f[0]
+        if int(f[4]) != len(rows):
+            raise ValueError("ranks of subject %s are not 0..n-1" % f[0])
+        ha, pa = f[1].rsplit(";", 1)
+        hb, pb = f[2].rsplit(";", 1)
+        rows.append((ha, pa, hb, pb, float(f[3])))
+    flush(rows)
+    return counts, stats
+
+
+def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
+    """The M-step on the device.  `lines_or_path`: input lines (a list) or the path of an input file; `config`: the
+    configuration dict of `load_config`.  The input is cut into blocks of `block_lines` lines; each is tokenised, imputed
+    as one device batch (em_mr on, phased output on, `em` as impute_file's) and its rows are added to the accumulator
+    where they lie.  `output_MUUG` stays as the configuration has it: the reference's phased pass starts from what the MUUG
+    pass left when that one ended in Plan C (impute.py:1637-1654), so the phased rows of some subjects differ with it off,
+    and the counts are those of the rows the configured run prints.  -> ({pop: {haplotype: count}}, stats); the cuts do not show in any bit of a count.
+    Subjects the device cannot answer follow `imputation.on_unsupported` as in `impute_lines_block`."""
+    from .imputation.impute import UnsupportedSubjects
+
+    if isinstance(lines_or_path, (str, bytes, os.PathLike)):
+        with open(lines_or_path) as fh:
+            lines = fh.read().splitlines()
+    else:
+        lines = [l.rstrip("\n") for l in lines_or_path]
+    if planb is None:
+        planb = config["planb"]
+    block_lines = max(1, int(block_lines))
+    g = imputation.netGraph
+    pops = imputation.populations
+    P = len(pops)
+    cfg = dict(config, output_haplotypes=True)
+    params = imputation._params(cfg, planb, True, em)
+    ps, keep = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
+    ctx = nat.default_context(imputation.device)
+    dgraph = g.device(ctx)
+    n_slots = len(g.full_loci)
+    acc = nat.EmAccumulator(ctx, [g.adict.count(s) for s in range(n_slots)], P, first_capacity)
+    host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
+    imputation.unsupported = []
+    spilled = {}  # (pop index, haplotype text) -> count: haplotypes that hold an allele the dictionary does not know
+    kernel_ms = 0.0
+    n_blocks = 0
+    try:
+        for lo in range(0, len(lines), block_lines):
+            text = "".join(l + "\n" for l in lines[lo:lo + block_lines]).encode()
+            parsed = nat.Parsed(g.adict, text, planb)
+            batch = None
+            try:
+                kinds = parsed.kinds()
+                dev = parsed.dev_index()
+                bad = [(lo + int(j), parsed.subject_id(int(j)), host_reason[int(kinds[j])]) for j in np.flatnonzero(np.isin(kinds, list(host_reason)))]
+                subj = parsed.subjects()
+                if len(subj):
+                    races = parsed.races()
+                    priors = np.ones((max(1, len(races)), P, P))
+                    for k, (r1, r2) in enumerate(races):
+                        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+                    batch = nat.DeviceBatch(ctx, dgraph, params, subj, parsed.tokens(), priors)
+                    batch.run()
+                    seen = acc.spill_count()
+                    acc.accumulate(batch)
+                    kernel_ms += acc.kernel_ms()
+                    n_blocks += 1
+                    line_of = {int(dev[j]): int(j) for j in np.flatnonzero(kinds == nat.K_DEVICE)}
+                    if acc.last_unsupported():
+                        res, _ = batch.results()
+                        bad += [(lo + line_of[int(i)], parsed.subject_id(line_of[int(i)]), int(res[i]["reason"]))
+                                for i in np.flatnonzero(res["status"] == nat.ST_UNSUPPORTED)]
+                    for rec in acc.spill(seen):
+                        line, key = line_of[int(rec["subject"])], int(rec["key"])
+                        fields = [(s, (key >> (nat.ABITS * s)) & 0xFFF) for s in range(n_slots)]
+                        name = "~".join(parsed.allele(line, s, a - 1) for s, a in fields if a)
+                        at = (int(rec["pop"]), name)
+                        spilled[at] = spilled[at] + float(rec["w"]) if at in spilled else float(rec["w"])
+                imputation.unsupported += sorted(bad)
+                if imputation.unsupported and imputation.on_unsupported == "raise":
+                    raise UnsupportedSubjects(imputation.unsupported)
+            finally:
+                if batch is not None:
+                    batch.close()
+                parsed.close()
+        keys, kpops, vals = acc.export()
+        counts = {}
+        names = {}
+        for key, p, v in zip(keys.tolist(), kpops.tolist(), vals.tolist()):
+            name = names.get(key)
+            if name is None:
+                name = names[key] = "~".join(x for x in g.key_alleles(key) if x)
+            counts.setdefault(pops[p], {})[name] = v
+        for (p, name), v in spilled.items():
+            counts.setdefault(pops[p], {})[name] = v
+        stats = acc.stats()
+        stats.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
+    finally:
+        acc.close()
+    return counts, stats
+
+
+def write_freq_files(counts, freq_data_dir, pops):
+    """One `POP.freqs.gz` per population in the format produce_hpf reads (generate_hpf.py:43-59): header
+    `Haplo,Count,Freq`, rows sorted by haplotype, Freq = Count / T with T the left-to-right sum of the file's counts in row
+    order, floats written with repr.  -> {pop: T}"""
+    os.makedirs(freq_data_dir, exist_ok=True)
+    totals = {}
+    for pop in pops:
+        rows = sorted(counts.get(pop, {}).items())
+        total = 0.0
+        for _, c in rows:
+            total = total + c
+        totals[pop] = total
+        with gzip.open(os.path.join(freq_data_dir, pop + ".freqs.gz"), "wt", newline="") as fh:
+            fh.write("Haplo,Count,Freq\n")
+            for hap, c in rows:
+                fh.write("%s,%r,%r\n" % (hap, c, c / total if total else 0.0))
+    return totals
+
+
+def em_iteration(conf_file, graph=None, block_lines=65536):
+    """One EM iteration on the configuration's own files: the M-step over `imputation_in_file` on `graph` (built from the
+    configuration's graph CSVs when None), new `POP.freqs.gz` into `freq_data_dir`, then produce_hpf and
+    graph_freqs(for_em=True, em_pop=populations).  -> (the new Graph, counts).  Paths are taken as the configuration gives
+    them, as everywhere in this package.  Whether and when the frequencies converge is the caller's business."""
+    import json
+
+    from graph_generation.generate_hpf import produce_hpf
+
+    from .grim import graph_freqs, graph_instance
+    from .imputation.impute import Imputation
+    from .run_impute_def import load_config
+
+    config, _ = load_config(conf_file)
+    with open(conf_file) as fh:
+        raw = json.load(fh)
+    if graph is None:
+        graph = graph_instance(config)
+    imp = Imputation(graph, config)
+    counts, stats = m_step_counts(imp, config["imputation_input_file"], config, block_lines=block_lines)
+    write_freq_files(counts, raw["freq_data_dir"], config["pops"])
+    produce_hpf(conf_file, quiet=True)
+    graph_freqs(conf_file, for_em=True, em_pop=config["pops"])
+    return graph_instance(config), counts

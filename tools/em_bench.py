@@ -1,0 +1,100 @@
+"""
+Measure the device M-step (grim/em.py, csrc/grim_em.h) on bench.py's config-4-shaped workload: the pop4 graph, 100 000
+mixed subjects of seed 3, MR priors, em_mr on.  One JSON line with three medians over --steps steps after --warmup:
+
+  (a) impute_kernel_ms   the batch's kernels, grim_batch_kernel_ms(0) in timing mode
+  (b) em_kernel_ms       grim_em_kernel_ms of the accumulate call on that batch (a fresh accumulator every step)
+  (c) text_route_s       what a caller had before: impute_lines_block text -> fold_pmug_text, wall time
+
+    python tools/em_bench.py [--subjects N] [--steps K] [--warmup W]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import timeit
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+import harness  # noqa: E402
+import synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--subjects", type=int, default=100000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--text-steps", type=int, default=3, help="steps of the text route (tens of seconds each at 100k subjects)")
+    args = ap.parse_args()
+
+    import numpy as np
+
+    import __graft_entry__ as ge
+    ge.build()
+    from grim import _native as nat
+    from grim.em import fold_pmug_text
+    from grim.imputation.impute import Imputation
+    from grim.imputation.networkx_graph import Graph
+    from grim.run_impute_def import load_config
+
+    pops = harness.POPS["pop4"]
+    work = harness.ensure_graph("pop4")
+    conf = harness.base_conf(pops)
+    conf["UNK_priors"] = "MR"
+    lines = synth.SubjectGen(synth.read_freqs(synth.CAU_FREQS), 3, pops=pops).mixed(args.subjects)
+    conf, cpath = harness._write_inputs(work, conf, lines[:1], "em_bench")
+    cwd = os.getcwd()
+    os.chdir(work)
+    try:
+        cfg, _ = load_config(cpath)
+        g = Graph(cfg).build_graph(cfg["node_file"], cfg["top_links_file"], cfg["edges_file"])
+        imp = Imputation(g, cfg)
+    finally:
+        os.chdir(cwd)
+    imp.on_unsupported = "skip"
+    imp.quiet = True
+    P = len(pops)
+    ctx = nat.default_context(imp.device)
+    params = imp._params(dict(cfg, output_haplotypes=True), cfg["planb"], True, True)
+    parsed = nat.Parsed(g.adict, ("\n".join(lines) + "\n").encode(), cfg["planb"])
+    ps, keep = nat.prior_spec(cfg["priority"], imp.unk_priors, imp.count_by_prob)
+    races = parsed.races()
+    priors = np.ones((max(1, len(races)), P, P))
+    for k, (r1, r2) in enumerate(races):
+        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+    batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
+    batch.set_timing(True)
+    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]
+    a_ms, b_ms, stats, entries = [], [], None, 0
+    for step in range(args.warmup + args.steps):
+        batch.run()
+        acc = nat.EmAccumulator(ctx, n_alleles, P)
+        try:
+            acc.accumulate(batch)
+            if step >= args.warmup:
+                a_ms.append(batch.kernel_ms(0))
+                b_ms.append(acc.kernel_ms())
+            stats, entries = acc.stats(), acc.entries()
+        finally:
+            acc.close()
+    batch.close()
+    parsed.close()
+    c_s = []
+    for step in range(args.text_steps):
+        t0 = timeit.default_timer()
+        texts = imp.impute_lines_block(lines, dict(cfg, output_haplotypes=True), em_mr=True, em=True)
+        counts, _ = fold_pmug_text(texts["pmug"])
+        c_s.append(timeit.default_timer() - t0)
+    print(json.dumps({
+        "workload": "pop4 graph, %d mixed subjects (seed 3), MR priors, em_mr" % args.subjects, "steps": args.steps, "warmup": args.warmup,
+        "impute_kernel_ms": statistics.median(a_ms), "em_kernel_ms": statistics.median(b_ms),
+        "text_route_s": statistics.median(c_s) if c_s else None, "text_steps": args.text_steps,
+        "em_stats": stats, "entries": entries, "text_entries": sum(len(d) for d in counts.values()) if c_s else None,
+    }))
+
+
+if __name__ == "__main__":
+    main()
