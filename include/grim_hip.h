@@ -213,11 +213,23 @@ int grim_batch_run_repeat(grim_batch *b, uint32_t n);
  * hipEvents on the launch stream (hipExtLaunchKernelGGL).  Off by default: a synchronous 10k-subject run costs
  * 22 us without, 29 us with the events. */
 int grim_batch_set_timing(grim_batch *b, int on);
-/* device time of the last grim_batch_run in timing mode (0 otherwise):
- * which = 0 all kernels, 1 half-wave + one-wave + general kernel, 2 plan-B/C kernel, 3 half-wave kernel, 4 general plan-A
- *         kernel, 5 one-wave kernel, 6 the table kernels, 7 the half-wave kernel's row compaction, 8 the device tokenizer,
- *         9 the mid-size kernel (each from the kernels' own start/stop events; 0 = 1 + 2 + 6 + 7 + 8);
- * which | 0x10 = the mean of that figure over all runs since timing was switched on */
+/* device time of the last grim_batch_run in timing mode (0 otherwise), each figure from the kernels' own start/stop
+ * events.  `which` is one of the values below (frozen: callers pass them as plain integers too); TOTAL = PLAN_A + PLAN_B +
+ * TABLES + COMPACT + TOKENIZER.  which | GRIM_MS_MEAN = the mean of that figure over all runs since timing was switched on;
+ * any other value gives 0. */
+enum {
+  GRIM_MS_TOTAL = 0,     /* all kernels */
+  GRIM_MS_PLAN_A = 1,    /* half-wave + one-wave + general + mid-size kernel */
+  GRIM_MS_PLAN_B = 2,    /* plan-B/C kernel */
+  GRIM_MS_HALF_WAVE = 3, /* half-wave kernel */
+  GRIM_MS_GENERAL = 4,   /* general plan-A kernel */
+  GRIM_MS_ONE_WAVE = 5,  /* one-wave kernel */
+  GRIM_MS_TABLES = 6,    /* the table kernels */
+  GRIM_MS_COMPACT = 7,   /* the half-wave kernel's row compaction */
+  GRIM_MS_TOKENIZER = 8, /* the device tokenizer */
+  GRIM_MS_MID = 9,       /* the mid-size kernel */
+  GRIM_MS_MEAN = 0x10
+};
 double grim_batch_kernel_ms(const grim_batch *b, int which);
 /* algorithmic byte counters of the last run: [0] probes, [1] CSR neighbour ids,
  * [2] frequency vectors gathered, [3] output rows */
@@ -339,7 +351,7 @@ typedef struct {
   double wall_s;                                     /* open -> finish */
   double tokenize_cpu_s, format_cpu_s, write_cpu_s;  /* summed over the worker threads */
   double device_s;                                   /* device thread busy: copies + kernels + waits */
-  double kernel_ms[7];                               /* sums of grim_batch_kernel_ms(which) over the chunks (timing mode) */
+  double kernel_ms[7];                               /* sums of grim_batch_kernel_ms over the chunks (timing mode): [GRIM_MS_TOTAL .. GRIM_MS_TABLES] */
   uint64_t counters[4];                              /* sums of grim_batch_counters */
   uint64_t text_bytes[7];
   uint64_t bytes_h2d, bytes_d2h;

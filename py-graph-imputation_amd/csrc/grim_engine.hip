@@ -266,7 +266,7 @@ __global__ void grim_finish_kernel(unsigned long long *state, unsigned long long
 struct grim_ctx {
   int device;
   hipStream_t stream;
-  hipStream_t copy_stream;  // D2H of a finished batch while the next batch's kernels run (engine_batch_fetch_async)
+  hipStream_t copy_stream;  // D2H of a finished batch while the next batch's kernels run (engine_batch_fetch_issue)
   hipStream_t up_stream;    // H2D of the next batch's input while this batch's kernels run (engine_batch_load)
   GrimSdma *sdma;           // results D2H on an SDMA engine of its own (grim_sdma.h); nullptr: export kernel / hipMemcpyAsync
   int export_mode;          // 2 = grim_sdma, 1 = grim_export_kernel, 0 = hipMemcpyAsync on the copy stream
@@ -294,6 +294,30 @@ struct grim_graph {
   uint64_t bytes;
   uint32_t max_label;
 };
+
+// Timing mode: one entry per timed interval of a run.  Each has a start/stop event pair in its batch, and a row below with
+// its public number (grim_batch_kernel_ms) and whether it counts into GRIM_MS_PLAN_A.  A new kernel of the run path is one
+// entry, one row and one launch(...) line.
+enum Phase { PH_HALF_WAVE, PH_ONE_WAVE, PH_MID, PH_GENERAL, PH_PLAN_B, PH_TABLES, PH_COMPACT, PH_TOKENIZER, PH_COUNT, PH_NONE = PH_COUNT };
+struct PhaseRow {
+  int which;
+  bool plan_a;
+};
+static constexpr PhaseRow PHASES[PH_COUNT] = {
+    {GRIM_MS_HALF_WAVE, true}, {GRIM_MS_ONE_WAVE, true}, {GRIM_MS_MID, true},      {GRIM_MS_GENERAL, true},
+    {GRIM_MS_PLAN_B, false},   {GRIM_MS_TABLES, false},  {GRIM_MS_COMPACT, false}, {GRIM_MS_TOKENIZER, false},
+};
+// every per-kernel value of the header, GRIM_MS_PLAN_B .. GRIM_MS_MID, is the number of exactly one phase
+static constexpr bool phases_match_header() {
+  for (int w = GRIM_MS_PLAN_B; w <= GRIM_MS_MID; ++w) {
+    int n = 0;
+    for (int p = 0; p < PH_COUNT; ++p) n += PHASES[p].which == w;
+    if (n != 1) return false;
+  }
+  return PH_COUNT == GRIM_MS_MID - GRIM_MS_PLAN_B + 1;
+}
+static_assert(phases_match_header(), "PHASES and the GRIM_MS_* values of grim_hip.h have drifted apart");
+static_assert(GRIM_MS_TOTAL == 0 && GRIM_MS_PLAN_A == 1 && GRIM_MS_MID < GRIM_MS_MEAN && GRIM_MS_MEAN == 0x10, "the GRIM_MS_* values are frozen");
 
 struct grim_batch {
   grim_ctx *ctx;
@@ -332,7 +356,6 @@ struct grim_batch {
   uint64_t off_subj;    // the input arena up to here is all a run without host-tokenised subjects needs
   uint32_t dev_lo, dev_hi, n_dev_lines, n_irregular;
   uint32_t n_host_small_waves;
-  float ms_k;           // timing mode: the tokenizer kernel
   uint32_t n_medium;
   uint32_t n_small, n_general, small_stride;
   uint64_t scratch_need;  // bytes of per-workgroup scratch this batch's runs need (bound at run time)
@@ -345,14 +368,13 @@ struct grim_batch {
   hipEvent_t ev_done;  // recorded behind the last kernel of a stage: what engine_batch_wait waits for (not the whole stream --
                        // the device thread may have queued the next chunk's kernels behind it already)
   bool enqueued;       // stage 1 is in flight (engine_batch_enqueue without its engine_batch_wait)
-  hipEvent_t ev[18];  // timing mode ([16]/[17] the mid-size kernel), kernel start/stop ([14]/[15] device tokenizer): [3]/[5] half-wave, [0]/[1] one-wave, [6]/[7] general, [4]/[2] Plan B,
-                      // [8]/[9] table kernels of stage 1, [10]/[11] table kernels after Plan B
+  hipEvent_t ev[PH_COUNT][2];  // timing mode: start/stop of every phase
+  uint32_t launched;  // timing mode: bit p = phase p was launched with its events and has not been read back yet
   bool timing;       // GRIM_TIMING=1 or grim_batch_set_timing: direct launches with per-kernel events instead of the graph replay
   hipGraphExec_t gexec;
   int graph_state;  // 0 not tried, 1 captured, -1 direct launches
-  float ms_a, ms_b, ms_s, ms_g, ms_m, ms_t, ms_c;  // ms_c: the half-wave kernel's row compaction
-  float ms_d;         // the mid-size kernel (grim_mid.h)
-  double acc_ms[10];  // sums over the timed runs since timing was switched on (index = `which`)
+  float ms[PH_COUNT];       // timing mode: the phases of the last run
+  double acc_ms[PH_COUNT];  // their sums over the timed runs since timing was switched on
   uint32_t n_timed;
   uint32_t rows_used;
   bool ran_ok = false;  // the last grim_batch_run finished and nothing was loaded since: res / rows hold its results (grim_em_accumulate)
@@ -827,7 +849,8 @@ grim_batch *engine_batch_create(grim_ctx *c, const grim_graph *g, const grim_par
       b->hstate = nullptr;
       ok = false;
     }
-    for (int i = 0; i < 18 && ok; ++i) ok = hipEventCreate(&b->ev[i]) == hipSuccess;
+    for (auto &pair : b->ev)
+      for (hipEvent_t &e : pair) ok = ok && hipEventCreate(&e) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&b->ev_done, hipEventDisableTiming | hipEventReleaseToSystem) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&b->ev_copy, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming) == hipSuccess;
@@ -1222,10 +1245,29 @@ static int bind_scratch(grim_batch *b) {
   return 0;
 }
 
+// Every kernel of a run is launched through here, on the context's stream.  Timing mode (b->timing) brackets the launch
+// with its phase's events (hipExtLaunchKernelGGL) and notes the phase for engine_batch_wait to read back; otherwise, and
+// for a kernel outside every timed interval (PH_NONE), it is a plain launch.  start/stop: an interval that spans several
+// kernels gives its first one the start event only and its last one the stop event only.
+template <typename... P, typename... Q>
+static void launch_span(grim_batch *b, Phase ph, bool start, bool stop, void (*kernel)(P...), dim3 grid, dim3 block, Q &&...args) {
+  if (b->timing && ph != PH_NONE) {
+    b->launched |= 1u << ph;
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, b->ctx->stream, start ? b->ev[ph][0] : nullptr, stop ? b->ev[ph][1] : nullptr, 0,
+                          static_cast<P>(args)...);
+  } else {
+    hipLaunchKernelGGL(kernel, grid, block, 0, b->ctx->stream, static_cast<P>(args)...);
+  }
+}
+template <typename... P, typename... Q>
+static void launch(grim_batch *b, Phase ph, void (*kernel)(P...), dim3 grid, dim3 block, Q &&...args) {
+  launch_span(b, ph, true, true, kernel, grid, block, args...);
+}
+
 // The table kernels: the one-wave kernel for work items of up to GRIM_TAB_T1_MAX pairs; split, bucket and merge kernel
 // for the rest.  All read their list lengths on the device (the kernels before them in the stream wrote them) and come
-// back at once when there is nothing to do.  start/stop: timing mode, one interval around the four.
-static void enqueue_tables(grim_batch *b, hipEvent_t start, hipEvent_t stop) {
+// back at once when there is nothing to do.  Timing mode: one interval around them all.
+static void enqueue_tables(grim_batch *b) {
   grim_ctx *c = b->ctx;
   DevArgs &A = b->a;
   const uint32_t cand = b->n_subj;
@@ -1253,50 +1295,38 @@ static void enqueue_tables(grim_batch *b, hipEvent_t start, hipEvent_t stop) {
   if (g4 == 0) g4 = 1;
   if (g5 == 0) g5 = 1;
   (void)hipMemsetAsync(c->wctr, 0, 4 * GRIM_WCTR_WORDS, c->stream);
-  if (start && stop) {
-    hipExtLaunchKernelGGL(grim_tables_wave_kernel, dim3(g1), dim3(64), 0, c->stream, start, nullptr, 0, A);
-  } else {
-    hipLaunchKernelGGL(grim_tables_wave_kernel, dim3(g1), dim3(64), 0, c->stream, A);
-  }
-  hipLaunchKernelGGL(grim_tables_split_wave_kernel, dim3(g4), dim3(64), 0, c->stream, A);
-  hipLaunchKernelGGL(grim_tables_split_kernel, dim3(g2), dim3(GRIM_WG), 0, c->stream, A);
-  hipLaunchKernelGGL(grim_tables_bucket_kernel, dim3(g3), dim3(64), 0, c->stream, A);
-  hipLaunchKernelGGL(grim_tables_merge_wave_kernel, dim3(g5), dim3(64), 0, c->stream, A);
-  if (start && stop) {
-    hipExtLaunchKernelGGL(grim_tables_merge_kernel, dim3(g2), dim3(GRIM_WG), 0, c->stream, nullptr, stop, 0, A);
-  } else {
-    hipLaunchKernelGGL(grim_tables_merge_kernel, dim3(g2), dim3(GRIM_WG), 0, c->stream, A);
-  }
+  launch_span(b, PH_TABLES, true, false, grim_tables_wave_kernel, dim3(g1), dim3(64), A);
+  launch(b, PH_NONE, grim_tables_split_wave_kernel, dim3(g4), dim3(64), A);
+  launch(b, PH_NONE, grim_tables_split_kernel, dim3(g2), dim3(GRIM_WG), A);
+  launch(b, PH_NONE, grim_tables_bucket_kernel, dim3(g3), dim3(64), A);
+  launch(b, PH_NONE, grim_tables_merge_wave_kernel, dim3(g5), dim3(64), A);
+  launch_span(b, PH_TABLES, false, true, grim_tables_merge_kernel, dim3(g2), dim3(GRIM_WG), A);
+}
+
+// The half-wave kernel over the `n` records at `recs`, and the compaction of its rows out of their fixed places in the staging
+// region from `stage` on.  order: the records' subjects (host-tokenised), or nullptr (device-tokenised: one record slot per
+// line).  Ak: the kernel's arguments (its slice of the per-wave counters).
+static void enqueue_half_wave(grim_batch *b, bool timed, const DevArgs &Ak, const SmallRec *recs, const uint32_t *order, uint32_t n, uint32_t stage) {
+  const uint32_t per_block = GRIM_WG / 32;
+  launch(b, timed ? PH_HALF_WAVE : PH_NONE, grim_plan_a_small_kernel, dim3((n + per_block - 1) / per_block), dim3(GRIM_WG), Ak, recs, n, stage,
+         b->small_stride);
+  launch(b, timed ? PH_COMPACT : PH_NONE, grim_small_compact_kernel, dim3((n + 63) / 64), dim3(64), b->a, order, order ? nullptr : recs, n, stage,
+         b->small_stride);
 }
 
 // Stage 1 of a run: half-wave kernel, one-wave kernel, general plan-A kernel, finish kernel (state to the pinned
 // host copy, device copy reset for the next run).  Default: launched directly.  GRIM_GRAPH=1: captured once per batch and
 // replayed as ONE hipGraph launch (no event nodes: they carry no timestamps when replayed on this runtime).
-// Timing mode: launched directly, every kernel bracketed by its own start/stop events (hipExtLaunchKernelGGL).
-static int enqueue_stage1(grim_batch *b, bool timing) {
+// Timing mode: launched directly, every kernel bracketed by its own start/stop events (launch).
+static int enqueue_stage1(grim_batch *b) {
   grim_ctx *c = b->ctx;
   DevArgs &A = b->a;
-  const uint32_t per_block = GRIM_WG / 32;
   // staging region of the half-wave kernel's rows, at the top of the pool: host-tokenised subjects first, then one slot per
   // line of the device tokenizer
   const uint32_t stage0 = (uint32_t)b->row_limit - (b->n_small + b->n_dev_lines) * b->small_stride;
-  const bool both = b->n_small && b->n_dev_lines;  // (timing mode brackets the device-tokenised launch when there are two)
-  if (b->n_small) {
-    const dim3 grid((b->n_small + per_block - 1) / per_block), block(GRIM_WG);
-    if (timing && !both)
-      hipExtLaunchKernelGGL(grim_plan_a_small_kernel, grid, block, 0, c->stream, b->ev[3], b->ev[5], 0, A,
-                            (const SmallRec *)b->d_small, b->n_small, stage0, b->small_stride);
-    else
-      hipLaunchKernelGGL(grim_plan_a_small_kernel, grid, block, 0, c->stream, A, (const SmallRec *)b->d_small, b->n_small, stage0,
-                         b->small_stride);
-    const dim3 cgrid((b->n_small + 63) / 64), cblock(64);
-    if (timing && !both)
-      hipExtLaunchKernelGGL(grim_small_compact_kernel, cgrid, cblock, 0, c->stream, b->ev[12], b->ev[13], 0, A,
-                            (const uint32_t *)b->d_os, (const SmallRec *)nullptr, b->n_small, stage0, b->small_stride);
-    else
-      hipLaunchKernelGGL(grim_small_compact_kernel, cgrid, cblock, 0, c->stream, A, (const uint32_t *)b->d_os, (const SmallRec *)nullptr,
-                         b->n_small, stage0, b->small_stride);
-  }
+  // A run with both kinds launches the half-wave pair twice.  The half-wave and compaction times are then those of the
+  // device-tokenised launch: the host-tokenised one goes out untimed (PH_NONE) rather than recording the same events first.
+  if (b->n_small) enqueue_half_wave(b, b->n_dev_lines == 0, A, b->d_small, b->d_os, b->n_small, stage0);
   if (b->n_dev_lines) {
     // GL strings -> half-wave records on the device, then the half-wave kernel over one record slot per line
     DevTok T;
@@ -1310,58 +1340,29 @@ static int enqueue_stage1(grim_batch *b, bool timing) {
     T.tok = const_cast<uint16_t *>(A.tok);
     T.tok_base = (uint32_t)(b->plan.tok_cap ? b->plan.tok_cap : 1);
     T.graph_loci = A.g.n_loci;
-    const dim3 tgrid((b->n_dev_lines + (GRIM_WG / 64) * TOK_LINES_PER_WAVE - 1) / ((GRIM_WG / 64) * TOK_LINES_PER_WAVE)), block(GRIM_WG);
-    if (timing)
-      hipExtLaunchKernelGGL(grim_tokenize_kernel, tgrid, block, 0, c->stream, b->ev[14], b->ev[15], 0, A, T);
-    else
-      hipLaunchKernelGGL(grim_tokenize_kernel, tgrid, block, 0, c->stream, A, T);
+    const dim3 tgrid((b->n_dev_lines + (GRIM_WG / 64) * TOK_LINES_PER_WAVE - 1) / ((GRIM_WG / 64) * TOK_LINES_PER_WAVE));
+    launch(b, PH_TOKENIZER, grim_tokenize_kernel, tgrid, dim3(GRIM_WG), A, T);
     DevArgs A2 = A;
     A2.small_ctr = A.small_ctr + 2 * b->n_host_small_waves;
-    const uint32_t stage_d = stage0 + b->n_small * b->small_stride;
-    const dim3 grid((b->n_dev_lines + per_block - 1) / per_block);
-    if (timing)
-      hipExtLaunchKernelGGL(grim_plan_a_small_kernel, grid, block, 0, c->stream, b->ev[3], b->ev[5], 0, A2,
-                            (const SmallRec *)b->d_dsmall, b->n_dev_lines, stage_d, b->small_stride);
-    else
-      hipLaunchKernelGGL(grim_plan_a_small_kernel, grid, block, 0, c->stream, A2, (const SmallRec *)b->d_dsmall, b->n_dev_lines, stage_d,
-                         b->small_stride);
-    const dim3 cgrid((b->n_dev_lines + 63) / 64), cblock(64);
-    if (timing)
-      hipExtLaunchKernelGGL(grim_small_compact_kernel, cgrid, cblock, 0, c->stream, b->ev[12], b->ev[13], 0, A, (const uint32_t *)nullptr,
-                            (const SmallRec *)b->d_dsmall, b->n_dev_lines, stage_d, b->small_stride);
-    else
-      hipLaunchKernelGGL(grim_small_compact_kernel, cgrid, cblock, 0, c->stream, A, (const uint32_t *)nullptr, (const SmallRec *)b->d_dsmall,
-                         b->n_dev_lines, stage_d, b->small_stride);
+    enqueue_half_wave(b, true, A2, b->d_dsmall, nullptr, b->n_dev_lines, stage0 + b->n_small * b->small_stride);
   }
   if (b->n_medium) {
     static const int waves_per_cu = env_int("GRIM_MEDIUM_WAVES", GRIM_MEDIUM_WAVES_PER_CU);
     uint32_t grid = (uint32_t)c->n_cu * (uint32_t)(waves_per_cu > 0 ? waves_per_cu : GRIM_MEDIUM_WAVES_PER_CU);
     if (grid > b->n_medium) grid = b->n_medium;
-    if (timing)
-      hipExtLaunchKernelGGL(grim_plan_a_medium_kernel, dim3(grid), dim3(64), 0, c->stream, b->ev[0], b->ev[1], 0, A,
-                            (const uint32_t *)b->d_om, b->n_medium, A.bail_list);
-    else
-      hipLaunchKernelGGL(grim_plan_a_medium_kernel, dim3(grid), dim3(64), 0, c->stream, A, (const uint32_t *)b->d_om,
-                         b->n_medium, A.bail_list);
+    launch(b, PH_ONE_WAVE, grim_plan_a_medium_kernel, dim3(grid), dim3(64), A, b->d_om, b->n_medium, A.bail_list);
   }
   if (A.mid_list && b->n_general + b->n_medium) {
     const uint32_t want = b->n_general + b->n_medium;
     uint32_t grid = (uint32_t)c->n_cu * GRIM_MID_WG_PER_CU;
     if (grid > want) grid = want;
-    if (timing)
-      hipExtLaunchKernelGGL(grim_plan_a_mid_kernel, dim3(grid), dim3(GRIM_WG), 0, c->stream, b->ev[16], b->ev[17], 0, A);
-    else
-      hipLaunchKernelGGL(grim_plan_a_mid_kernel, dim3(grid), dim3(GRIM_WG), 0, c->stream, A);
+    launch(b, PH_MID, grim_plan_a_mid_kernel, dim3(grid), dim3(GRIM_WG), A);
   }
   if (b->n_general + b->n_medium) {
     uint32_t want = b->n_general + b->n_medium;
-    const dim3 grid(b->n_slots < want ? b->n_slots : want), block(GRIM_WG);
-    if (timing)
-      hipExtLaunchKernelGGL(grim_plan_a_kernel, grid, block, 0, c->stream, b->ev[6], b->ev[7], 0, A);
-    else
-      hipLaunchKernelGGL(grim_plan_a_kernel, grid, block, 0, c->stream, A);
+    launch(b, PH_GENERAL, grim_plan_a_kernel, dim3(b->n_slots < want ? b->n_slots : want), dim3(GRIM_WG), A);
   }
-  hipLaunchKernelGGL(grim_finish_kernel, dim3(1), dim3(GRIM_WG), 0, c->stream, A.counters, b->hstate, 0u, 0);
+  launch(b, PH_NONE, grim_finish_kernel, dim3(1), dim3(GRIM_WG), A.counters, b->hstate, 0u, 0);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1396,7 +1397,8 @@ int engine_batch_enqueue(grim_batch *b) {
     set_err(c, "grim_batch_run: output row pool smaller than the half-wave kernel's fixed region");
     return -2;
   }
-  b->ms_s = b->ms_a = b->ms_g = b->ms_m = b->ms_t = b->ms_c = b->ms_b = b->ms_k = b->ms_d = 0;
+  memset(b->ms, 0, sizeof(b->ms));
+  b->launched = 0;
   std::lock_guard<std::mutex> lk(c->run_mu);
   if (bind_scratch(b) != 0) return -1;
   if (b->up_pending) {
@@ -1411,7 +1413,7 @@ int engine_batch_enqueue(grim_batch *b) {
     }
   }
   if (b->timing) {
-    if (enqueue_stage1(b, true) != 0) {
+    if (enqueue_stage1(b) != 0) {
       set_err(c, "grim_batch_run: kernel launch failed");
       return -1;
     }
@@ -1422,7 +1424,7 @@ int engine_batch_enqueue(grim_batch *b) {
       // 26.9 us per synchronous run, launching its two kernels directly 21.8 us -- so the replay is opt-in
       static const int use_graph = env_int("GRIM_GRAPH", 0);
       if (use_graph && hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        int rc = enqueue_stage1(b, false);
+        int rc = enqueue_stage1(b);
         hipGraph_t gr = nullptr;
         hipError_t e = hipStreamEndCapture(c->stream, &gr);
         if (rc == 0 && e == hipSuccess && gr && hipGraphInstantiate(&b->gexec, gr, nullptr, nullptr, 0) == hipSuccess)
@@ -1433,13 +1435,21 @@ int engine_batch_enqueue(grim_batch *b) {
     }
     if (b->graph_state == 1) {
       HIPCHK(hipGraphLaunch(b->gexec, c->stream), c, -1);
-    } else if (enqueue_stage1(b, false) != 0) {
+    } else if (enqueue_stage1(b) != 0) {
       set_err(c, "grim_batch_run: kernel launch failed");
       return -1;
     }
   }
   HIPCHK(hipEventRecord(b->ev_done, c->stream), c, -1);
   b->enqueued = true;
+  return 0;
+}
+
+// the times of the phases launched since the last call (timing mode; the caller has waited for the kernels)
+static int read_phase_times(grim_batch *b) {
+  for (int p = 0; p < PH_COUNT; ++p)
+    if (b->launched >> p & 1) HIPCHK(hipEventElapsedTime(&b->ms[p], b->ev[p][0], b->ev[p][1]), b->ctx, -1);
+  b->launched = 0;
   return 0;
 }
 
@@ -1455,15 +1465,7 @@ int engine_batch_wait(grim_batch *b) {
   b->enqueued = false;
   b->ran_ok = false;
   HIPCHK(hipEventSynchronize(b->ev_done), c, -1);
-  if (b->timing) {
-    if (b->n_small || b->n_dev_lines) HIPCHK(hipEventElapsedTime(&b->ms_s, b->ev[3], b->ev[5]), c, -1);
-    if (b->n_medium) HIPCHK(hipEventElapsedTime(&b->ms_m, b->ev[0], b->ev[1]), c, -1);
-    if (b->n_general + b->n_medium) HIPCHK(hipEventElapsedTime(&b->ms_g, b->ev[6], b->ev[7]), c, -1);
-    if (A.mid_list && b->n_general + b->n_medium) HIPCHK(hipEventElapsedTime(&b->ms_d, b->ev[16], b->ev[17]), c, -1);
-    if (b->n_small || b->n_dev_lines) HIPCHK(hipEventElapsedTime(&b->ms_c, b->ev[12], b->ev[13]), c, -1);
-    if (b->n_dev_lines) HIPCHK(hipEventElapsedTime(&b->ms_k, b->ev[14], b->ev[15]), c, -1);
-    b->ms_a = b->ms_s + b->ms_m + b->ms_g + b->ms_d;
-  }
+  if (read_phase_times(b) != 0) return -1;
   uint32_t head[GRIM_NQ];
   memcpy(head, b->hstate + GRIM_NCTR, 4 * GRIM_NQ);
   // ---- stage 2: Plan B / C when the first stage left subjects for it, then the table kernels ONCE over the accepted
@@ -1474,29 +1476,25 @@ int engine_batch_wait(grim_batch *b) {
       std::lock_guard<std::mutex> lk(c->run_mu);
       if (bind_scratch(b) != 0) return -1;
       if (run_b) {
+        // the plan-A kernels leave the list of subjects in next_list/next_count
         uint32_t grid = b->n_slots < head[2] + head[6] ? b->n_slots : head[2] + head[6];
-        if (grim_launch_plan_b(A, grid, c->stream, b->timing ? b->ev[4] : nullptr, b->timing ? b->ev[2] : nullptr) != 0) {
+        launch(b, PH_PLAN_B, grim_plan_b_kernel, dim3(grid), dim3(GRIM_WG), A);
+        if (hipGetLastError() != hipSuccess) {
           set_err(c, "grim_batch_run: plan-B launch failed");
           return -1;
         }
       }
-      enqueue_tables(b, b->timing ? b->ev[10] : nullptr, b->timing ? b->ev[11] : nullptr);
-      hipLaunchKernelGGL(grim_finish_kernel, dim3(1), dim3(GRIM_WG), 0, c->stream, A.counters, b->hstate, 0u, 1);
+      enqueue_tables(b);
+      launch(b, PH_NONE, grim_finish_kernel, dim3(1), dim3(GRIM_WG), A.counters, b->hstate, 0u, 1);
       HIPCHK(hipGetLastError(), c, -1);
       HIPCHK(hipEventRecord(b->ev_done, c->stream), c, -1);
     }
     HIPCHK(hipEventSynchronize(b->ev_done), c, -1);
-    if (b->timing) {
-      float t2 = 0;
-      if (run_b) HIPCHK(hipEventElapsedTime(&b->ms_b, b->ev[4], b->ev[2]), c, -1);
-      HIPCHK(hipEventElapsedTime(&t2, b->ev[10], b->ev[11]), c, -1);
-      b->ms_t += t2;
-    }
+    if (read_phase_times(b) != 0) return -1;
     memcpy(head, b->hstate + GRIM_NCTR, 4 * GRIM_NQ);
   }
   if (b->timing) {
-    const double v[10] = {(double)b->ms_a + b->ms_b + b->ms_t + b->ms_c + b->ms_k, b->ms_a, b->ms_b, b->ms_s, b->ms_g, b->ms_m, b->ms_t, b->ms_c, b->ms_k, b->ms_d};
-    for (int k = 0; k < 10; ++k) b->acc_ms[k] += v[k];
+    for (int p = 0; p < PH_COUNT; ++p) b->acc_ms[p] += b->ms[p];
     b->n_timed++;
   }
   static const int dbg_classes = env_int("GRIM_DEBUG_CLASSES", 0);
@@ -1566,20 +1564,13 @@ extern "C" int grim_batch_run_repeat(grim_batch *b, uint32_t n) {
 
 extern "C" double grim_batch_kernel_ms(const grim_batch *b, int which) {
   if (!b) return 0.0;
-  if (which & 0x10) {  // mean over the timed runs since grim_batch_set_timing(b, 1)
-    const int k = which & 0xF;
-    return (k < 10 && b->n_timed) ? b->acc_ms[k] / b->n_timed : 0.0;
-  }
-  if (which == 1) return b->ms_a;
-  if (which == 2) return b->ms_b;
-  if (which == 3) return b->ms_s;
-  if (which == 4) return b->ms_g;
-  if (which == 5) return b->ms_m;
-  if (which == 6) return b->ms_t;
-  if (which == 7) return b->ms_c;
-  if (which == 8) return b->ms_k;
-  if (which == 9) return b->ms_d;
-  return (double)b->ms_a + (double)b->ms_b + (double)b->ms_t + (double)b->ms_c + (double)b->ms_k;
+  const bool mean = (which & GRIM_MS_MEAN) != 0;  // over the timed runs since grim_batch_set_timing(b, 1)
+  const int w = which & ~GRIM_MS_MEAN;
+  if (mean && !b->n_timed) return 0.0;
+  double sum = 0.0;
+  for (int p = 0; p < PH_COUNT; ++p)
+    if (w == GRIM_MS_TOTAL || w == PHASES[p].which || (w == GRIM_MS_PLAN_A && PHASES[p].plan_a)) sum += mean ? b->acc_ms[p] : b->ms[p];
+  return mean ? sum / b->n_timed : sum;
 }
 
 extern "C" int grim_batch_counters(const grim_batch *cb, uint64_t out[4]) {
@@ -1605,68 +1596,8 @@ extern "C" int grim_batch_counters(const grim_batch *cb, uint64_t out[4]) {
 
 extern "C" uint32_t grim_batch_total_rows(const grim_batch *b) { return b ? b->rows_used : 0; }
 
-static int batch_fetch_on(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst, hipStream_t st);
-int engine_batch_fetch(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst) {
-  return b ? batch_fetch_on(b, res_lo, res_hi, rows_dst, b->ctx->stream) : -1;
-}
-// the whole batch's results over the context's copy stream: the caller has synchronised the kernels (grim_batch_run
-// returned) and may run the NEXT batch's kernels while this copy is in flight; any thread
-int engine_batch_fetch_async(grim_batch *b) { return b ? batch_fetch_on(b, 0, b->n_subj, nullptr, b->ctx->copy_stream) : -1; }
-// the same in two halves: the copy is queued on the copy stream with an event behind it (issue), another thread waits for
-// that event (wait) -- so the thread that watches the kernels is not held up by a PCIe transfer
-static int batch_fetch_on(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst, hipStream_t st, bool wait);
-// GRIM_DEBUG_COPYTIME (diagnostic): the D2H's own duration by a pair of timing events on the copy stream
-static std::atomic<uint64_t> g_ct_ns, g_ct_n;
-static hipEvent_t g_ct_ev[2][64];
-static std::atomic<uint32_t> g_ct_k;
-static int ct_on() {
-  static const int on = [] {
-    const int v = env_int("GRIM_DEBUG_COPYTIME", 0);
-    if (v) {
-      for (int i = 0; i < 64; ++i) { (void)hipEventCreate(&g_ct_ev[0][i]); (void)hipEventCreate(&g_ct_ev[1][i]); }
-      atexit([] { if (g_ct_n.load()) fprintf(stderr, "grim: D2H on the copy stream: %.1f us average over %llu copies\n", g_ct_ns.load() / 1e3 / (double)g_ct_n.load(), (unsigned long long)g_ct_n.load()); });
-    }
-    return v;
-  }();
-  return on;
-}
-int engine_batch_fetch_issue(grim_batch *b) {
-  if (!b) return -1;
-  if (ct_on()) {
-    const uint32_t k = g_ct_k.fetch_add(1) & 63;
-    b->ct_slot = (int)k;
-    (void)hipEventRecord(g_ct_ev[0][k], b->ctx->copy_stream);
-    if (batch_fetch_on(b, 0, b->n_subj, nullptr, b->ctx->copy_stream, false) != 0) return -1;
-    (void)hipEventRecord(g_ct_ev[1][k], b->ctx->copy_stream);
-    HIPCHK(hipEventRecord(b->ev_copy, b->ctx->copy_stream), b->ctx, -1);
-    return 0;
-  }
-  if (batch_fetch_on(b, 0, b->n_subj, nullptr, b->ctx->copy_stream, false) != 0) return -1;
-  if (!b->fetch_hsa) HIPCHK(hipEventRecord(b->ev_copy, b->ctx->copy_stream), b->ctx, -1);
-  return 0;
-}
-int engine_batch_fetch_wait(grim_batch *b) {
-  if (!b) return -1;
-  use_device(b->ctx->device);
-  if (b->fetch_hsa) {
-    b->fetch_hsa = false;
-    if (grim_sdma_wait(b->ctx->sdma, b->sdma_job) != 0) {
-      set_err(b->ctx, "engine_batch_fetch: the SDMA copy of the results failed");
-      return -1;
-    }
-    return 0;
-  }
-  HIPCHK(hipEventSynchronize(b->ev_copy), b->ctx, -1);
-  if (ct_on() && b->ct_slot >= 0) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, g_ct_ev[0][b->ct_slot], g_ct_ev[1][b->ct_slot]) == hipSuccess) { g_ct_ns += (uint64_t)(ms * 1e6); ++g_ct_n; }
-    b->ct_slot = -1;
-  }
-  return 0;
-}
-static int batch_fetch_on(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst, hipStream_t st) {
-  return batch_fetch_on(b, res_lo, res_hi, rows_dst, st, true);
-}
+// D2H of result headers [res_lo, res_hi) and the rows into the pinned landing area (rows: or `rows_dst`) on stream `st`;
+// wait: until the copies are over
 static int batch_fetch_on(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst, hipStream_t st, bool wait) {
   if (!b) return -1;
   grim_ctx *c = b->ctx;
@@ -1726,6 +1657,59 @@ static int batch_fetch_on(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_
   return 0;
 }
 
+int engine_batch_fetch(grim_batch *b, uint32_t res_lo, uint32_t res_hi, grim_row *rows_dst) {
+  return b ? batch_fetch_on(b, res_lo, res_hi, rows_dst, b->ctx->stream, true) : -1;
+}
+// The whole batch's results over the context's copy stream: the caller has synchronised the kernels (engine_batch_wait
+// returned) and may run the NEXT batch's kernels while this copy is in flight.  In two halves: the copy is queued on the
+// copy stream with an event behind it (issue), another thread waits for that event (wait) -- so the thread that watches
+// the kernels is not held up by a PCIe transfer.
+// GRIM_DEBUG_COPYTIME (diagnostic): the D2H's own duration by a pair of timing events on the copy stream
+static std::atomic<uint64_t> g_ct_ns, g_ct_n;
+static hipEvent_t g_ct_ev[2][64];
+static std::atomic<uint32_t> g_ct_k;
+static int ct_on() {
+  static const int on = [] {
+    const int v = env_int("GRIM_DEBUG_COPYTIME", 0);
+    if (v) {
+      for (int i = 0; i < 64; ++i) { (void)hipEventCreate(&g_ct_ev[0][i]); (void)hipEventCreate(&g_ct_ev[1][i]); }
+      atexit([] { if (g_ct_n.load()) fprintf(stderr, "grim: D2H on the copy stream: %.1f us average over %llu copies\n", g_ct_ns.load() / 1e3 / (double)g_ct_n.load(), (unsigned long long)g_ct_n.load()); });
+    }
+    return v;
+  }();
+  return on;
+}
+int engine_batch_fetch_issue(grim_batch *b) {
+  if (!b) return -1;
+  const bool ct = ct_on() != 0;
+  if (ct) {
+    b->ct_slot = (int)(g_ct_k.fetch_add(1) & 63);
+    (void)hipEventRecord(g_ct_ev[0][b->ct_slot], b->ctx->copy_stream);
+  }
+  if (batch_fetch_on(b, 0, b->n_subj, nullptr, b->ctx->copy_stream, false) != 0) return -1;
+  if (ct) (void)hipEventRecord(g_ct_ev[1][b->ct_slot], b->ctx->copy_stream);
+  if (ct || !b->fetch_hsa) HIPCHK(hipEventRecord(b->ev_copy, b->ctx->copy_stream), b->ctx, -1);
+  return 0;
+}
+int engine_batch_fetch_wait(grim_batch *b) {
+  if (!b) return -1;
+  use_device(b->ctx->device);
+  if (b->fetch_hsa) {
+    b->fetch_hsa = false;
+    if (grim_sdma_wait(b->ctx->sdma, b->sdma_job) != 0) {
+      set_err(b->ctx, "engine_batch_fetch: the SDMA copy of the results failed");
+      return -1;
+    }
+    return 0;
+  }
+  HIPCHK(hipEventSynchronize(b->ev_copy), b->ctx, -1);
+  if (ct_on() && b->ct_slot >= 0) {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, g_ct_ev[0][b->ct_slot], g_ct_ev[1][b->ct_slot]) == hipSuccess) { g_ct_ns += (uint64_t)(ms * 1e6); ++g_ct_n; }
+    b->ct_slot = -1;
+  }
+  return 0;
+}
 extern "C" int grim_batch_results(grim_batch *b, grim_subject_result *res, grim_row *rows) {
   if (!b) return -1;
   grim_ctx *c = b->ctx;
@@ -1741,8 +1725,9 @@ static void batch_destroy(grim_batch *b) {
   if (!b) return;
   use_device(b->ctx->device);
   hipStreamSynchronize(b->ctx->stream);
-  for (int i = 0; i < 18; ++i)
-    if (b->ev[i]) hipEventDestroy(b->ev[i]);
+  for (auto &pair : b->ev)
+    for (hipEvent_t e : pair)
+      if (e) hipEventDestroy(e);
   if (b->ev_done) hipEventDestroy(b->ev_done);
   if (b->ev_copy) hipEventDestroy(b->ev_copy);
   if (b->fetch_hsa && b->ctx->sdma) (void)grim_sdma_wait(b->ctx->sdma, b->sdma_job);  // (an abandoned stream: the copy still writes h_out)

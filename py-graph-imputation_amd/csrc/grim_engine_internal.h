@@ -54,10 +54,8 @@ uint64_t engine_bytes_moved(const grim_batch *b, int dir);  // 0 = H2D, 1 = D2H 
 void engine_set_error(grim_ctx *ctx, const char *msg);
 // hand a batch back to its context: the next engine_batch_create on that context reuses its arenas
 void engine_batch_recycle(grim_batch *b);
-// after a run that returned -2: 1 = the pair pool ran out and the next load will make it big enough (run the same subjects
-// again), 0 = split the batch
-int engine_batch_fetch_async(grim_batch *b);
-// ... in two halves: queue the copy (an event behind it) / wait for that event, possibly on another thread
+// the whole batch's results over the context's copy stream, in two halves: queue the copy (an event behind it) / wait for
+// that event, possibly on another thread
 int engine_batch_fetch_issue(grim_batch *b);
 int engine_batch_fetch_wait(grim_batch *b);
 // a run in two halves (grim_batch_run = enqueue + wait): stage 1 is launched behind whatever the context's stream holds and
@@ -79,6 +77,8 @@ uint32_t engine_batch_irregular(const grim_batch *b);
 uint32_t engine_graph_order_bad(const grim_graph *g);
 uint64_t engine_batch_pool_want(const grim_batch *b);
 void engine_batch_hint_pool(grim_batch *b, uint64_t records);
+// after a run that returned -2: 1 = the pair pool ran out and the next load will make it big enough (run the same subjects
+// again), 0 = split the batch
 int engine_batch_grow_pool(grim_batch *b, uint64_t max_records);
 int engine_batch_grow_rows(grim_batch *b, uint64_t max_rows);
 uint64_t engine_batch_row_limit(const grim_batch *b);

@@ -393,7 +393,7 @@ static void run_tokenize(grim_stream *s, Chunk *c, uint32_t r) {
 static std::atomic<uint64_t> g_dbg_ns[12];  // [4] reader: scan + copy + dispatch, [5] reader: waiting for a free chunk slot, [6] next_records: waiting  // GRIM_DEBUG_STREAM: staging / load + launch (device thread), wait + stage 2 / fetch (copy thread)
 
 struct PartStats {  // what a part's run adds to the stream's statistics (applied under the lock by the caller)
-  double kernel_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+  double kernel_ms[GRIM_MS_TABLES + 1] = {};  // grim_stream_stats.kernel_ms: GRIM_MS_TOTAL .. GRIM_MS_TABLES
   uint64_t counters[4] = {0, 0, 0, 0};
   uint64_t reruns = 0;
 };
@@ -444,7 +444,8 @@ static int stage_part(grim_stream *s, Chunk *c, uint32_t lo, uint32_t hi, size_t
 
 static void part_stats(grim_stream *s, grim_batch *b, PartStats &ps) {
   if (!s->opt.timing) return;
-  for (int k = 0; k < 7; ++k) ps.kernel_ms[k] += grim_batch_kernel_ms(b, k);
+  static_assert(sizeof(ps.kernel_ms) == sizeof(grim_stream_stats::kernel_ms), "kernel_ms: seven slots, GRIM_MS_TOTAL .. GRIM_MS_TABLES");
+  for (int w = GRIM_MS_TOTAL; w <= GRIM_MS_TABLES; ++w) ps.kernel_ms[w] += grim_batch_kernel_ms(b, w);
   uint64_t ctr[4];
   if (grim_batch_counters(b, ctr) == 0)
     for (int k = 0; k < 4; ++k) ps.counters[k] += ctr[k];
@@ -760,7 +761,7 @@ static void copy_loop(grim_stream *s) {
     tl_note(c, 6);
     {
       std::lock_guard<std::mutex> lk(s->mu);
-      for (int k = 0; k < 7; ++k) s->st.kernel_ms[k] += ps.kernel_ms[k];
+      for (int w = GRIM_MS_TOTAL; w <= GRIM_MS_TABLES; ++w) s->st.kernel_ms[w] += ps.kernel_ms[w];
       for (int k = 0; k < 4; ++k) s->st.counters[k] += ps.counters[k];
       s->st.reruns += ps.reruns;
       if (rc != 0 || !fetched_ok) {

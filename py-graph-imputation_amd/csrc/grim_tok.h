@@ -38,7 +38,7 @@ struct DevDict {
 };
 
 // hash of a packed name (both sides build and probe the tables with it)
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define GRIM_HD __host__ __device__
 #else
 #define GRIM_HD

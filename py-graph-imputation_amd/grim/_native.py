@@ -18,6 +18,10 @@ MAXROWS = 8
 
 ST_OK, ST_MISS, ST_UNSUPPORTED, ST_NOPHASE = 0, 1, 2, 3
 T_UMUG, T_UMUG_POPS, T_PMUG, T_PMUG_POPS = 0, 1, 2, 3
+# `which` of DeviceBatch.kernel_ms (GRIM_MS_* in grim_hip.h); MS_MEAN | x = the mean of x over the timed runs
+(MS_TOTAL, MS_PLAN_A, MS_PLAN_B, MS_HALF_WAVE, MS_GENERAL, MS_ONE_WAVE, MS_TABLES, MS_COMPACT, MS_TOKENIZER,
+ MS_MID) = range(10)
+MS_MEAN = 0x10
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GRIM_LIB") or os.path.join(os.path.dirname(_HERE), "libgrim_hip.so")
@@ -270,7 +274,8 @@ class DeviceBatch:
         """start/stop hipEvents around every kernel of a run (resets the accumulated means); see grim_batch_set_timing"""
         lib().grim_batch_set_timing(self.h, 1 if on else 0)
 
-    def kernel_ms(self, which=0):
+    def kernel_ms(self, which=MS_TOTAL):
+        """device time of the last run in timing mode: which = one of MS_*, | MS_MEAN for the mean over the timed runs"""
         return float(lib().grim_batch_kernel_ms(self.h, which))
 
     def counters(self):

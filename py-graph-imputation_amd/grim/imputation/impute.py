@@ -328,8 +328,8 @@ class Imputation(object):
         t2 = timeit.default_timer()
         self.last_stats = {
             "upload_s": t0 - tu, "download_s": t2 - t1,
-            "n": n, "run_s": t1 - t0, "kernel_ms": batch.kernel_ms(0), "kernel_a_ms": batch.kernel_ms(1),
-            "kernel_b_ms": batch.kernel_ms(2), "counters": batch.counters(),
+            "n": n, "run_s": t1 - t0, "kernel_ms": batch.kernel_ms(nat.MS_TOTAL), "kernel_a_ms": batch.kernel_ms(nat.MS_PLAN_A),
+            "kernel_b_ms": batch.kernel_ms(nat.MS_PLAN_B), "counters": batch.counters(),
         }
         if keep:
             return res, rows, batch
@@ -538,7 +538,7 @@ class Imputation(object):
             self.last_stats = {
                 "n": int(stats.subjects), "lines": int(stats.lines), "chunks": int(stats.chunks), "reruns": int(stats.reruns),
                 "wall_s": stats.wall_s, "total_s": timeit.default_timer() - t0, "device_s": stats.device_s,
-                "kernel_ms": stats.kernel_ms[0], "kernel_a_ms": stats.kernel_ms[1], "kernel_b_ms": stats.kernel_ms[2],
+                "kernel_ms": stats.kernel_ms[nat.MS_TOTAL], "kernel_a_ms": stats.kernel_ms[nat.MS_PLAN_A], "kernel_b_ms": stats.kernel_ms[nat.MS_PLAN_B],
                 "counters": [int(x) for x in stats.counters],
                 "host_s": {"tokenize_cpu": stats.tokenize_cpu_s, "format_cpu": stats.format_cpu_s, "write_cpu": stats.write_cpu_s},
                 "text_bytes": [int(x) for x in stats.text_bytes],
@@ -605,8 +605,8 @@ class Imputation(object):
         t2 = timeit.default_timer()
         self.last_stats = {
             "upload_s": t0 - tu, "download_s": t2 - t1,
-            "n": len(subj), "run_s": t1 - t0, "kernel_ms": batch.kernel_ms(0), "kernel_a_ms": batch.kernel_ms(1),
-            "kernel_b_ms": batch.kernel_ms(2), "counters": batch.counters(),
+            "n": len(subj), "run_s": t1 - t0, "kernel_ms": batch.kernel_ms(nat.MS_TOTAL), "kernel_a_ms": batch.kernel_ms(nat.MS_PLAN_A),
+            "kernel_b_ms": batch.kernel_ms(nat.MS_PLAN_B), "counters": batch.counters(),
         }
         batch.close()
         return res, rows

@@ -519,15 +519,17 @@ def test_timing_mode_and_repeat():
         batch.set_timing(False)
         batch.run()
         res0, rows0 = batch.results()
-        assert batch.kernel_ms(0) == 0.0
+        assert batch.kernel_ms(nat.MS_TOTAL) == 0.0
         batch.set_timing(True)
         batch.run_repeat(5)
         res1, rows1 = batch.results()
-        assert batch.kernel_ms(3) > 0.0 and batch.kernel_ms(2) > 0.0  # half-wave kernel and Plan B both ran
-        total = sum(batch.kernel_ms(w) for w in (3, 5, 9, 4, 2, 6, 7))  # half-wave, one-wave, mid-size, general, Plan B, table kernels, row compaction
-        assert batch.kernel_ms(9) > 0.0  # the mid-size kernel took the mixed subjects the one-wave kernel handed on
-        assert abs(batch.kernel_ms(0) - total) < 1e-6
-        assert batch.kernel_ms(0x10 | 3) > 0.0
+        assert batch.kernel_ms(nat.MS_HALF_WAVE) > 0.0 and batch.kernel_ms(nat.MS_PLAN_B) > 0.0  # half-wave kernel and Plan B both ran
+        assert (nat.MS_HALF_WAVE, nat.MS_ONE_WAVE, nat.MS_MID, nat.MS_GENERAL, nat.MS_PLAN_B, nat.MS_TABLES, nat.MS_COMPACT) == (3, 5, 9, 4, 2, 6, 7)
+        total = sum(batch.kernel_ms(w) for w in (nat.MS_HALF_WAVE, nat.MS_ONE_WAVE, nat.MS_MID, nat.MS_GENERAL, nat.MS_PLAN_B, nat.MS_TABLES,
+                                                 nat.MS_COMPACT))
+        assert batch.kernel_ms(nat.MS_MID) > 0.0  # the mid-size kernel took the mixed subjects the one-wave kernel handed on
+        assert abs(batch.kernel_ms(nat.MS_TOTAL) - total) < 1e-6
+        assert nat.MS_MEAN == 0x10 and batch.kernel_ms(nat.MS_MEAN | nat.MS_HALF_WAVE) > 0.0
 
         def tables(res, rows):  # row offsets depend on the order in which workgroups took rows; contents must not
             out = []

@@ -290,6 +290,16 @@ def test_device_tokenizer_equals_host_tokenizer(monkeypatch):
     for k in nat.TEXT_KEYS:
         assert t1[k] == t0[k], k
     assert st1.bytes_h2d > 0 and st1.subjects == st0.subjects == 3000
+    # timing mode, by either tokenizer: the half-wave kernel ran, and the total (nat.MS_TOTAL) holds more than Plan A,
+    # Plan B and the table kernels -- the row compaction and, on the device, the tokenizer ran too
+    for st in (st1, st0):
+        assert st.kernel_ms[nat.MS_HALF_WAVE] > 0
+        assert st.kernel_ms[nat.MS_TOTAL] > st.kernel_ms[nat.MS_PLAN_A] + st.kernel_ms[nat.MS_PLAN_B] + st.kernel_ms[nat.MS_TABLES]
+    # chunks that hold host-tokenised AND device-tokenised small subjects: both half-wave launches in one timed run
+    tm, stm, _ = _stream_texts(imp, cfg, lines, chunk_lines=700, n_threads=3, depth=3, timing=True)
+    for k in nat.TEXT_KEYS:
+        assert tm[k] == out["1", "small"][k], k
+    assert stm.kernel_ms[nat.MS_HALF_WAVE] > 0
 
 
 def test_one_big_write_whose_pieces_divide_evenly():

@@ -2,7 +2,7 @@
 Measure the device M-step (grim/em.py, csrc/grim_em.h) on bench.py's config-4-shaped workload: the pop4 graph, 100 000
 mixed subjects of seed 3, MR priors, em_mr on.  One JSON line with three medians over --steps steps after --warmup:
 
-  (a) impute_kernel_ms   the batch's kernels, grim_batch_kernel_ms(0) in timing mode
+  (a) impute_kernel_ms   the batch's kernels, grim_batch_kernel_ms(GRIM_MS_TOTAL) in timing mode
   (b) em_kernel_ms       grim_em_kernel_ms of the accumulate call on that batch (a fresh accumulator every step)
   (c) text_route_s       what a caller had before: impute_lines_block text -> fold_pmug_text, wall time
 
@@ -75,7 +75,7 @@ def main():
         try:
             acc.accumulate(batch)
             if step >= args.warmup:
-                a_ms.append(batch.kernel_ms(0))
+                a_ms.append(batch.kernel_ms(nat.MS_TOTAL))
                 b_ms.append(acc.kernel_ms())
             stats, entries = acc.stats(), acc.entries()
         finally:

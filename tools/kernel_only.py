@@ -80,9 +80,10 @@ def main():
     ctr = batch.counters()
     ctr[3] = int(res["n_rows"].sum())
     algo = (8 * len(subj) + 2 * n_tok) + 16 * ctr[0] + 4 * ctr[1] + 8 * P * ctr[2] + 24 * ctr[3]
-    names = {3: "grim_plan_a_small_kernel", 7: "grim_small_compact_kernel", 5: "grim_plan_a_medium_kernel", 9: "grim_plan_a_mid_kernel",
-             4: "grim_plan_a_kernel", 2: "grim_plan_b_kernel", 6: "grim_tables_*"}
-    ms = {v: batch.kernel_ms(0x10 | k) for k, v in names.items()} if not args.no_timing else {}
+    names = {nat.MS_HALF_WAVE: "grim_plan_a_small_kernel", nat.MS_COMPACT: "grim_small_compact_kernel",
+             nat.MS_ONE_WAVE: "grim_plan_a_medium_kernel", nat.MS_MID: "grim_plan_a_mid_kernel", nat.MS_GENERAL: "grim_plan_a_kernel",
+             nat.MS_PLAN_B: "grim_plan_b_kernel", nat.MS_TABLES: "grim_tables_*"}
+    ms = {v: batch.kernel_ms(nat.MS_MEAN | k) for k, v in names.items()} if not args.no_timing else {}
     out = {"workload": desc, "subjects": len(subj), "runs": args.runs, "algorithmic_bytes_per_launch": int(algo),
            "hip_event_mean_ms": ms}
     dom = max(ms, key=ms.get) if ms else None
