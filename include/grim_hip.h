@@ -455,6 +455,48 @@ uint64_t grim_em_last_unsupported(const grim_em *em);
 double grim_em_kernel_ms(const grim_em *em);
 void grim_em_free(grim_em *em);
 
+/* ======================= marginal genotype tables on a subset of the loci (csrc/grim_marginal.h) ======================
+ * What scripts/reduce_loci.py does to a printed .umug file -- drop a locus from every genotype, add the probabilities of
+ * genotypes that became equal, sort again, keep the top rows -- on the genotype rows a finished batch holds in HBM, for any
+ * set of kept loci.
+ * keep_mask: bit s = locus slot s is kept.  Per subject with status GRIM_ST_OK, GRIM_T_UMUG rows k = 0.. in rank order,
+ * row k = (a_k, b_k, p_k):
+ *   reduced genotype of row k: for every kept slot the UNORDERED pair of the slot's 12-bit fields of a_k and b_k (compared
+ *     on (min, max): which haplotype carries which allele is not canonical between rows); bit GRIM_KEY_GRAPH_ORDER and the
+ *     fields outside keep_mask are dropped; a field of 0 (locus not typed) is a value like any other;
+ *   group: the first row of a reduced genotype leads it; its sum = (p_leader + p_j) + p_l ... over its rows in rank order
+ *     (left-to-right fp64, no atomics, no tree sums);
+ *   rank: sums descending, ties in the leaders' order (stable): the number of groups with a larger sum, or an equal sum and
+ *     an earlier leader;
+ *   output: the first min(groups, max_rows) groups as grim_row records (a, b = the leader's keys masked to the kept slots,
+ *     prob = the sum, popa = popb = 0) and a grim_subject_result copy (status / plan / reason copied, n_genotypes = groups,
+ *     n_rows[GRIM_T_UMUG] = rows written, row_off[GRIM_T_UMUG] into the output rows, everything else 0).  Subjects that are
+ *     not GRIM_ST_OK or have no GRIM_T_UMUG rows, or whose rows do not lie inside the rows given, produce no rows.
+ * Not defined: a row whose a and b occupy different sets of slots (grim_format pairs the printed alleles by index); such
+ * subjects are counted in the statistics and the caller decides.
+ * The records print through grim_format with out_muug = 1, out_haps = 0 (text 0); every subject is independent, so the cuts
+ * of the input into batches cannot show. */
+typedef struct grim_marginal grim_marginal;
+grim_marginal *grim_marginal_create(grim_ctx *ctx, uint32_t keep_mask, uint32_t max_rows);
+/* after grim_batch_run; synchronous; reads the batch's device arrays, copies no result of the batch down.  -3 and a
+ * grim_last_error text, nothing launched and the reducer left empty, when the batch belongs to another context, holds no
+ * finished run, was built with out_muug off, or keep_mask is 0 or has bits outside the graph's loci */
+int grim_marginal_reduce(grim_marginal *m, grim_batch *b);
+/* the same on host records as grim_batch_results / grim_stream_next_records hand them out: res[n_subjects], rows[n_rows]
+ * are uploaded and run through the same kernels (-3 when keep_mask is 0 or has bits from GRIM_MAXL up) */
+int grim_marginal_reduce_records(grim_marginal *m, const grim_subject_result *res, uint32_t n_subjects, const grim_row *rows,
+                                 uint64_t n_rows);
+/* of the last reduce: result copies, and the extent of the output rows (subject regions lie apart: use row_off) */
+uint32_t grim_marginal_subjects(const grim_marginal *m);
+uint32_t grim_marginal_total_rows(const grim_marginal *m);
+/* res[grim_marginal_subjects], rows[grim_marginal_total_rows]; rows no region uses are zero */
+int grim_marginal_results(grim_marginal *m, grim_subject_result *res, grim_row *rows);
+/* of the last reduce: [0] subjects reduced [1] rows in [2] groups [3] rows out [4] subjects with a row that is not defined */
+int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]);
+/* device time of the last reduce: its kernels between their own start/stop events */
+double grim_marginal_kernel_ms(const grim_marginal *m);
+void grim_marginal_free(grim_marginal *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include "grim_tables.h"
 #include "grim_tokdev.h"
 #include "grim_em.h"
+#include "grim_marginal.h"
 #include "grim_engine_internal.h"
 #include "grim_host_internal.h"
 #include "grim_sdma.h"
@@ -2056,5 +2057,196 @@ extern "C" int grim_em_export(grim_em *e, uint64_t *keys, uint32_t *pops, double
     set_err(c, "grim_em_export: fewer entries than counted (internal)");
     return -1;
   }
+  return 0;
+}
+
+// =================================================================================================
+// Marginal genotype tables (grim_marginal.h): the UMUG rows of a finished batch reduced to a subset of the loci
+// =================================================================================================
+struct grim_marginal {
+  grim_ctx *ctx;
+  uint32_t keep_mask, max_rows;
+  unsigned long long *d_stat;
+  // kept and grown: region starts per subject; scratch, output rows and result copies; the uploaded records of
+  // grim_marginal_reduce_records
+  uint32_t *d_first;
+  MgScratch G;
+  grim_row *d_orows, *d_in_rows;
+  grim_subject_result *d_ores, *d_in_res;
+  uint64_t subj_cap, row_cap, in_subj_cap, in_row_cap;
+  // the last reduce
+  uint32_t n_subj, n_rows;
+  uint64_t stat[5];
+  hipEvent_t ev[2];
+  double last_ms;
+};
+
+extern "C" grim_marginal *grim_marginal_create(grim_ctx *c, uint32_t keep_mask, uint32_t max_rows) {
+  if (!c || max_rows == 0) {
+    set_err(c, "grim_marginal_create: bad arguments");
+    return nullptr;
+  }
+  use_device(c->device);
+  grim_marginal *m = new grim_marginal();
+  m->ctx = c;
+  m->keep_mask = keep_mask;
+  m->max_rows = max_rows;
+  bool ok = hipMalloc((void **)&m->d_stat, 8 * MG_S_COUNT * MG_S_SLICES) == hipSuccess;
+  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&m->ev[k]) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    set_err(c, "grim_marginal_create: device allocation failed");
+    grim_marginal_free(m);
+    return nullptr;
+  }
+  return m;
+}
+
+extern "C" void grim_marginal_free(grim_marginal *m) {
+  if (!m) return;
+  use_device(m->ctx->device);
+  hipStreamSynchronize(m->ctx->stream);
+  void *dev[] = {m->d_stat, m->d_first, m->G.lo, m->G.hi, m->G.prob, m->G.sum, m->G.lead, m->d_orows, m->d_in_rows, m->d_ores, m->d_in_res};
+  for (void *p : dev)
+    if (p) hipFree(p);
+  for (int k = 0; k < 2; ++k)
+    if (m->ev[k]) hipEventDestroy(m->ev[k]);
+  delete m;
+}
+
+static void mg_clear(grim_marginal *m) {
+  m->n_subj = m->n_rows = 0;
+  for (uint64_t &x : m->stat) x = 0;
+  m->last_ms = 0.0;
+}
+
+// the three launches on n subjects whose rows lie in [0, rows_used) of `rows` (device arrays)
+static int mg_run(grim_marginal *m, const char *who, const grim_subject_result *res, const grim_row *rows, uint32_t n, uint32_t rows_used) {
+  grim_ctx *c = m->ctx;
+  hipStream_t st = c->stream;
+  if (n == 0) return 0;
+  if ((uint64_t)n + 1 > m->subj_cap) {
+    m->subj_cap = 0;
+    if (!em_grow(m->d_first, (uint64_t)n + 1) || !em_grow(m->d_ores, (uint64_t)n)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    m->subj_cap = (uint64_t)n + 1;
+  }
+  if (rows_used > m->row_cap) {
+    const uint64_t want = (uint64_t)rows_used + rows_used / 4;
+    m->row_cap = 0;
+    if (!em_grow(m->G.lo, want) || !em_grow(m->G.hi, want) || !em_grow(m->G.prob, want) || !em_grow(m->G.sum, want) ||
+        !em_grow(m->G.lead, want) || !em_grow(m->d_orows, want)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    m->row_cap = want;
+  }
+  HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MG_S_COUNT * MG_S_SLICES, st), c, -1);
+  if (rows_used) HIPCHK(hipMemsetAsync(m->d_orows, 0, sizeof(grim_row) * (uint64_t)rows_used, st), c, -1);  // what a region does not use reads as zeros
+  HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
+  hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, m->d_first);
+  hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, m->d_first, n);
+  hipLaunchKernelGGL(mg_reduce_kernel, dim3(n), dim3(64), 0, st, res, rows, n, rows_used, m->d_first, rows_used, m->keep_mask, m->max_rows,
+                     m->G, m->d_ores, m->d_orows, m->d_stat);
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(m->ev[1], st), c, -1);
+  unsigned long long hs[MG_S_COUNT * MG_S_SLICES], h[MG_S_COUNT] = {0};
+  uint32_t total = 0;
+  HIPCHK(hipMemcpyAsync(hs, m->d_stat, sizeof(hs), hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipMemcpyAsync(&total, m->d_first + n, 4, hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  for (uint32_t k = 0; k < MG_S_COUNT * MG_S_SLICES; ++k) h[k % MG_S_COUNT] += hs[k];
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]), c, -1);
+  if (total > rows_used || h[MG_S_ROWS_IN] != total) {  // regions that overlap: the kernel left those that did not fit alone
+    set_err(c, std::string(who) + ": the subjects' genotype rows overlap (more rows than there are)");
+    return -1;
+  }
+  m->last_ms = ms;
+  m->n_subj = n;
+  m->n_rows = total;
+  for (int k = 0; k < 5; ++k) m->stat[k] = h[k];
+  return 0;
+}
+
+extern "C" int grim_marginal_reduce(grim_marginal *m, grim_batch *b) {
+  if (!m || !b) return -1;
+  grim_ctx *c = m->ctx;
+  mg_clear(m);
+  if (b->ctx != c) {
+    set_err(c, "grim_marginal_reduce: the batch belongs to another context");
+    return -3;
+  }
+  if (!b->ran_ok) {
+    set_err(c, "grim_marginal_reduce: the batch holds no finished run (call grim_batch_run first)");
+    return -3;
+  }
+  if (!b->a.prm.out_muug) {
+    set_err(c, "grim_marginal_reduce: the batch was built with out_muug off: it holds no genotype rows");
+    return -3;
+  }
+  if (m->keep_mask == 0 || b->g->d.n_loci > GRIM_MAXL || (m->keep_mask >> b->g->d.n_loci) != 0) {
+    set_err(c, "grim_marginal_reduce: keep_mask is empty or names a locus slot the graph does not have");
+    return -3;
+  }
+  use_device(c->device);
+  return mg_run(m, "grim_marginal_reduce", b->a.res, b->a.rows, b->n_subj, b->rows_used);
+}
+
+extern "C" int grim_marginal_reduce_records(grim_marginal *m, const grim_subject_result *res, uint32_t n_subjects, const grim_row *rows,
+                                            uint64_t n_rows) {
+  if (!m) return -1;
+  grim_ctx *c = m->ctx;
+  mg_clear(m);
+  if (m->keep_mask == 0 || (m->keep_mask >> GRIM_MAXL) != 0) {
+    set_err(c, "grim_marginal_reduce_records: keep_mask is empty or names a locus slot beyond GRIM_MAXL");
+    return -3;
+  }
+  if ((n_subjects && !res) || (n_rows && !rows) || n_rows > 0x7FFFFFFFull) {
+    set_err(c, "grim_marginal_reduce_records: bad arguments");
+    return -3;
+  }
+  use_device(c->device);
+  if (n_subjects == 0) return 0;
+  if (n_subjects > m->in_subj_cap) {
+    m->in_subj_cap = 0;
+    if (!em_grow(m->d_in_res, (uint64_t)n_subjects)) {
+      set_err(c, "grim_marginal_reduce_records: device allocation failed");
+      return -1;
+    }
+    m->in_subj_cap = n_subjects;
+  }
+  if (n_rows + 1 > m->in_row_cap) {  // never an empty allocation
+    m->in_row_cap = 0;
+    if (!em_grow(m->d_in_rows, n_rows + 1)) {
+      set_err(c, "grim_marginal_reduce_records: device allocation failed");
+      return -1;
+    }
+    m->in_row_cap = n_rows + 1;
+  }
+  HIPCHK(hipMemcpyAsync(m->d_in_res, res, sizeof(grim_subject_result) * (uint64_t)n_subjects, hipMemcpyHostToDevice, c->stream), c, -1);
+  if (n_rows) HIPCHK(hipMemcpyAsync(m->d_in_rows, rows, sizeof(grim_row) * n_rows, hipMemcpyHostToDevice, c->stream), c, -1);
+  HIPCHK(hipStreamSynchronize(c->stream), c, -1);  // the caller's arrays are free again
+  return mg_run(m, "grim_marginal_reduce_records", m->d_in_res, m->d_in_rows, n_subjects, (uint32_t)n_rows);
+}
+
+extern "C" uint32_t grim_marginal_subjects(const grim_marginal *m) { return m ? m->n_subj : 0; }
+extern "C" uint32_t grim_marginal_total_rows(const grim_marginal *m) { return m ? m->n_rows : 0; }
+extern "C" double grim_marginal_kernel_ms(const grim_marginal *m) { return m ? m->last_ms : 0.0; }
+
+extern "C" int grim_marginal_results(grim_marginal *m, grim_subject_result *res, grim_row *rows) {
+  if (!m || (m->n_subj && !res) || (m->n_rows && !rows)) return -1;
+  grim_ctx *c = m->ctx;
+  use_device(c->device);
+  if (m->n_subj) HIPCHK(hipMemcpy(res, m->d_ores, sizeof(grim_subject_result) * (size_t)m->n_subj, hipMemcpyDeviceToHost), c, -1);
+  if (m->n_rows) HIPCHK(hipMemcpy(rows, m->d_orows, sizeof(grim_row) * (size_t)m->n_rows, hipMemcpyDeviceToHost), c, -1);
+  return 0;
+}
+
+extern "C" int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]) {
+  if (!m || !out) return -1;
+  for (int k = 0; k < 5; ++k) out[k] = m->stat[k];
   return 0;
 }

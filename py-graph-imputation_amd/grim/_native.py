@@ -409,6 +409,106 @@ class EmAccumulator:
             pass
 
 
+# ---- marginal genotype tables (grim_marginal_*): the UMUG rows of finished batches reduced to a subset of the loci ----
+EXPORTS += [
+    "grim_marginal_create", "grim_marginal_reduce", "grim_marginal_reduce_records", "grim_marginal_subjects",
+    "grim_marginal_total_rows", "grim_marginal_results", "grim_marginal_stats", "grim_marginal_kernel_ms", "grim_marginal_free",
+]
+
+_marginal_ready = False
+
+
+def _marginal_lib():
+    global _marginal_ready
+    L = lib()
+    if not _marginal_ready:
+        L.grim_marginal_create.restype = C.c_void_p
+        L.grim_marginal_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        L.grim_marginal_reduce.restype = C.c_int
+        L.grim_marginal_reduce.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_marginal_reduce_records.restype = C.c_int
+        L.grim_marginal_reduce_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
+        L.grim_marginal_subjects.restype = C.c_uint32
+        L.grim_marginal_subjects.argtypes = [C.c_void_p]
+        L.grim_marginal_total_rows.restype = C.c_uint32
+        L.grim_marginal_total_rows.argtypes = [C.c_void_p]
+        L.grim_marginal_results.restype = C.c_int
+        L.grim_marginal_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_marginal_stats.restype = C.c_int
+        L.grim_marginal_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.grim_marginal_kernel_ms.restype = C.c_double
+        L.grim_marginal_kernel_ms.argtypes = [C.c_void_p]
+        L.grim_marginal_free.argtypes = [C.c_void_p]
+        _marginal_ready = True
+    return L
+
+
+MARGINAL_STATS = ("subjects", "rows_in", "groups", "rows_out", "undefined")
+
+
+class MarginalReducer:
+    """grim_marginal: the genotype rows of a finished batch (or of host records) grouped on the kept locus slots, summed in
+    rank order and ranked again, per subject, on the device (include/grim_hip.h, the grim_marginal_* block).  results(),
+    stats() and kernel_ms() speak of the last reduce."""
+
+    def __init__(self, ctx, keep_mask, max_rows):
+        L = _marginal_lib()
+        self.ctx = ctx
+        self.h = L.grim_marginal_create(ctx.h, int(keep_mask), int(max_rows))
+        if not self.h:
+            raise NativeError("grim_marginal_create failed: " + ctx.error())
+
+    def reduce(self, batch):
+        """one DeviceBatch after its run(), where its rows lie; synchronous"""
+        rc = _marginal_lib().grim_marginal_reduce(self.h, batch.h)
+        if rc != 0:
+            raise NativeError("grim_marginal_reduce failed (%d): %s" % (rc, self.ctx.error()))
+
+    def reduce_records(self, res, rows):
+        """host records (RESULT_DT[n], ROW_DT[m]) through the same kernels"""
+        res = np.ascontiguousarray(res, dtype=RESULT_DT)
+        rows = np.ascontiguousarray(rows, dtype=ROW_DT)
+        rc = _marginal_lib().grim_marginal_reduce_records(self.h, _ptr(res) if res.size else None, res.shape[0],
+                                                          _ptr(rows) if rows.size else None, rows.shape[0])
+        if rc != 0:
+            raise NativeError("grim_marginal_reduce_records failed (%d): %s" % (rc, self.ctx.error()))
+
+    def subjects(self):
+        return int(_marginal_lib().grim_marginal_subjects(self.h))
+
+    def total_rows(self):
+        return int(_marginal_lib().grim_marginal_total_rows(self.h))
+
+    def results(self):
+        """-> (res RESULT_DT[subjects], rows ROW_DT[total_rows]): subject i's rows are rows[res[i].row_off[0]:][:res[i].n_rows[0]]"""
+        L = _marginal_lib()
+        n, m = self.subjects(), self.total_rows()
+        res = np.zeros(n, dtype=RESULT_DT)
+        rows = np.zeros(max(m, 1), dtype=ROW_DT)
+        if L.grim_marginal_results(self.h, _ptr(res), _ptr(rows)) != 0:
+            raise NativeError("grim_marginal_results failed: " + self.ctx.error())
+        return res, rows[:m]
+
+    def stats(self):
+        out = (C.c_uint64 * 5)()
+        _marginal_lib().grim_marginal_stats(self.h, out)
+        return {k: int(v) for k, v in zip(MARGINAL_STATS, out)}
+
+    def kernel_ms(self):
+        return float(_marginal_lib().grim_marginal_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            _marginal_lib().grim_marginal_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ======================================================================================================
 # host-side helpers of the library (C++: allele dictionary, tokenizer, formatter) -- no GPU needed
 # ======================================================================================================
