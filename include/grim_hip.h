@@ -497,6 +497,64 @@ int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]);
 double grim_marginal_kernel_ms(const grim_marginal *m);
 void grim_marginal_free(grim_marginal *m);
 
+/* ======================= match probabilities between imputed subjects (csrc/grim_match.h) ==============================
+ * For every (patient, donor) pair the probability of 0, 1, 2, ... allele mismatches over a set K of kept loci (a 10/10, a
+ * 9/10, an 8/8 match) and the per-locus match probabilities, from the genotype rows the two sides' batches hold; the
+ * reference stops at the printed .umug files.
+ * keep_mask: bit s = locus slot s is in K.  n_alleles[slot] = the dictionary size when the sides were tokenised (as
+ * grim_em_create takes it).  Of a subject its GRIM_T_UMUG rows k = 0..n-1 in rank order are used, row k = (a_k, b_k, p_k).
+ *   flags per subject (both sides):
+ *     GRIM_MATCH_VALID      status GRIM_ST_OK, n >= 1, row_off / n_rows inside the rows given, and
+ *                           total = ((p_0 + p_1) + p_2) + ... (fp64, left to right) finite and > 0
+ *     GRIM_MATCH_PRIVATE    a row holds, in a slot of K, a key field above n_alleles[slot]: an allele private to the subject
+ *     GRIM_MATCH_UNDEFINED  a row has a slot (any) typed on one haplotype and 0 on the other
+ *     (PRIVATE and UNDEFINED are looked for whenever the subject's rows can be read, whatever the total)
+ *   weights w_k = p_k / total; bit GRIM_KEY_GRAPH_ORDER and the fields outside K are dropped;
+ *   row pair, patient row i = (a, b), donor row j = (c, d), per slot s of K with the 12-bit fields x1, x2 of a, b and y1, y2
+ *     of c, d: eq(x, y) = x == y and x != 0 (an untyped field equals nothing);
+ *     mm_s = 2 - max(eq(x1,y1) + eq(x2,y2), eq(x1,y2) + eq(x2,y1)); M(i,j) = the sum of mm_s over K, in 0..2|K|;
+ *   pair record, every sum in this order (w the patient's weights, v the donor's):
+ *     H[*] = 0.0, L[*] = 0.0
+ *     for j = 0..n_d-1 (donor rows, rank order):
+ *       ph[*] = 0.0, pl[*] = 0.0
+ *       for i = 0..n_p-1 (patient rows, rank order): t = w_i * v_j (one multiply, no fma); ph[M(i,j)] = ph[M(i,j)] + t;
+ *                                                    for s in K with mm_s == 0: pl[s] = pl[s] + t
+ *       H[m] = H[m] + ph[m] for every m, L[s] = L[s] + pl[s] for every s in K
+ *     mm[m] = H[m] (0.0 for m > 2|K|), locus[s] = L[s] for s in K and 0.0 elsewhere: equal inputs give equal bits.
+ *   A pair is computed iff both subjects are VALID and neither is PRIVATE; otherwise its record is all zero bytes (the caller
+ *   matches pairs left out for PRIVATE by allele text, grim_parsed_allele).  Results are patient-major: out[p * donors + d]. */
+#define GRIM_MATCH_MAX_PAIRS (1u << 24) /* patients x donors of one run: 2 GiB of result records */
+#define GRIM_MATCH_VALID 1
+#define GRIM_MATCH_PRIVATE 2
+#define GRIM_MATCH_UNDEFINED 4
+typedef struct {
+  double mm[2 * GRIM_MAXL + 1]; /* mm[m]: probability of m mismatching alleles over K */
+  double locus[GRIM_MAXL];      /* locus[s]: probability of no mismatch at slot s */
+} grim_match_rec; /* 128 bytes */
+typedef struct grim_match grim_match;
+grim_match *grim_match_create(grim_ctx *ctx, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL]);
+/* the patients as host records (grim_batch_results hands them out): uploaded, prepared on the device and kept across runs
+ * until set again.  Every call below answers -3 with a grim_last_error text, launches nothing and leaves no results (donors
+ * 0, statistics 0, kernel_ms 0; a refused grim_match_set_patients leaves no patients either) when it refuses:
+ * keep_mask is 0 or has bits from GRIM_MAXL up (here and in grim_match_run_records) or bits outside the graph's loci
+ * (grim_match_run); the batch belongs to another context, holds no finished run or was built with out_muug off; no patients
+ * were set; patients x donors is above GRIM_MATCH_MAX_PAIRS. */
+int grim_match_set_patients(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows);
+/* the subjects of a finished batch as donors, where their rows lie in HBM; synchronous; copies no result of the batch down */
+int grim_match_run(grim_match *m, grim_batch *donors);
+/* the same with donors given as host records */
+int grim_match_run_records(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows);
+uint32_t grim_match_patients(const grim_match *m); /* as set */
+uint32_t grim_match_donors(const grim_match *m);   /* of the last run */
+/* of the last run: out[patients * donors], patient_flags[patients], donor_flags[donors]; a null pointer skips that part */
+int grim_match_results(grim_match *m, grim_match_rec *out, uint8_t *patient_flags, uint8_t *donor_flags);
+/* of the last run (all 0 when it had no donors): [0] patients valid [1] donors valid [2] patients private [3] donors private
+ * [4] subjects of either side with a row that is not defined [5] pairs computed [6] row pairs evaluated [7] 0 */
+int grim_match_stats(const grim_match *m, uint64_t out[8]);
+/* device time of the last run: preparing the donors, clearing the records and the pair kernel between start/stop events */
+double grim_match_kernel_ms(const grim_match *m);
+void grim_match_free(grim_match *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@
 #include "grim_tokdev.h"
 #include "grim_em.h"
 #include "grim_marginal.h"
+#include "grim_match.h"
 #include "grim_engine_internal.h"
 #include "grim_host_internal.h"
 #include "grim_sdma.h"
@@ -2248,5 +2249,306 @@ extern "C" int grim_marginal_results(grim_marginal *m, grim_subject_result *res,
 extern "C" int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]) {
   if (!m || !out) return -1;
   for (int k = 0; k < 5; ++k) out[k] = m->stat[k];
+  return 0;
+}
+
+// =================================================================================================
+// Match probabilities (grim_match.h): the UMUG rows of patients against those of a finished batch of donors
+// =================================================================================================
+struct MtBuf {  // one side on the device, kept and grown
+  uint32_t *first;
+  uint64_t *a, *b;
+  double *w;
+  uint8_t *flags;
+  uint64_t subj_cap, row_cap;
+  uint32_t n;  // subjects of the side
+};
+
+struct grim_match {
+  grim_ctx *ctx;
+  uint32_t keep_mask;
+  EmLimits lim;
+  unsigned long long *d_stat;
+  MtBuf P, D;
+  // kept and grown: the uploaded records of grim_match_set_patients / grim_match_run_records; the result records
+  grim_row *d_in_rows;
+  grim_subject_result *d_in_res;
+  uint64_t in_subj_cap, in_row_cap;
+  double *d_out;
+  uint64_t out_cap;  // pairs
+  bool have_patients;
+  uint64_t pstat[MT_S_COUNT];  // what preparing the patients counted
+  // the last run
+  uint32_t n_donors;
+  uint64_t stat[8];
+  hipEvent_t ev[2];
+  double last_ms;
+};
+
+extern "C" grim_match *grim_match_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL]) {
+  if (!c || !n_alleles) {
+    set_err(c, "grim_match_create: bad arguments");
+    return nullptr;
+  }
+  use_device(c->device);
+  grim_match *m = new grim_match();
+  m->ctx = c;
+  m->keep_mask = keep_mask;
+  for (int q = 0; q < GRIM_MAXL; ++q) m->lim.n_alleles[q] = n_alleles[q];
+  bool ok = hipMalloc((void **)&m->d_stat, 8 * MT_S_COUNT * MT_S_SLICES) == hipSuccess;
+  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&m->ev[k]) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    set_err(c, "grim_match_create: device allocation failed");
+    grim_match_free(m);
+    return nullptr;
+  }
+  return m;
+}
+
+extern "C" void grim_match_free(grim_match *m) {
+  if (!m) return;
+  use_device(m->ctx->device);
+  hipStreamSynchronize(m->ctx->stream);
+  void *dev[] = {m->d_stat, m->P.first, m->P.a, m->P.b, m->P.w, m->P.flags, m->D.first, m->D.a, m->D.b, m->D.w, m->D.flags,
+                 m->d_in_rows, m->d_in_res, m->d_out};
+  for (void *p : dev)
+    if (p) hipFree(p);
+  for (int k = 0; k < 2; ++k)
+    if (m->ev[k]) hipEventDestroy(m->ev[k]);
+  delete m;
+}
+
+// no results: what a refusal leaves behind (the patients stay as they are)
+static void mt_clear(grim_match *m) {
+  m->n_donors = 0;
+  for (uint64_t &x : m->stat) x = 0;
+  m->last_ms = 0.0;
+}
+
+static void mt_drop_patients(grim_match *m) {
+  m->have_patients = false;
+  m->P.n = 0;
+  for (uint64_t &x : m->pstat) x = 0;
+}
+
+// the statistics block of the device, slices added up
+static int mt_read_stat(grim_match *m, uint64_t h[MT_S_COUNT]) {
+  grim_ctx *c = m->ctx;
+  unsigned long long hs[MT_S_COUNT * MT_S_SLICES];
+  HIPCHK(hipMemcpyAsync(hs, m->d_stat, sizeof(hs), hipMemcpyDeviceToHost, c->stream), c, -1);
+  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+  for (uint32_t k = 0; k < MT_S_COUNT; ++k) h[k] = 0;
+  for (uint32_t k = 0; k < MT_S_COUNT * MT_S_SLICES; ++k) h[k % MT_S_COUNT] += hs[k];
+  return 0;
+}
+
+// count, scan, prepare: n subjects whose rows lie in [0, rows_used) of `rows` (device arrays) into side S; enqueues only
+static int mt_prepare(grim_match *m, const char *who, MtBuf &S, uint32_t side, const grim_subject_result *res, const grim_row *rows,
+                      uint32_t n, uint32_t rows_used) {
+  grim_ctx *c = m->ctx;
+  hipStream_t st = c->stream;
+  if ((uint64_t)n + 1 > S.subj_cap) {
+    S.subj_cap = 0;
+    if (!em_grow(S.first, (uint64_t)n + 1) || !em_grow(S.flags, (uint64_t)n + 1)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    S.subj_cap = (uint64_t)n + 1;
+  }
+  if ((uint64_t)rows_used + 1 > S.row_cap) {  // never an empty allocation
+    const uint64_t want = (uint64_t)rows_used + rows_used / 4 + 1;
+    S.row_cap = 0;
+    if (!em_grow(S.a, want) || !em_grow(S.b, want) || !em_grow(S.w, want)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    S.row_cap = want;
+  }
+  hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, S.first);
+  hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, S.first, n);
+  hipLaunchKernelGGL(mt_prepare_kernel, dim3((n + 3) / 4), dim3(256), 0, st, res, rows, n, rows_used, S.first, rows_used, m->keep_mask,
+                     m->lim, side, S.a, S.b, S.w, S.flags, m->d_stat);
+  HIPCHK(hipGetLastError(), c, -1);
+  return 0;
+}
+
+// res[n], rows[n_rows] of the host into the upload buffers; the caller's arrays are free again on return
+static int mt_upload(grim_match *m, const char *who, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
+  grim_ctx *c = m->ctx;
+  if ((uint64_t)n + 1 > m->in_subj_cap) {
+    m->in_subj_cap = 0;
+    if (!em_grow(m->d_in_res, (uint64_t)n + 1)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    m->in_subj_cap = (uint64_t)n + 1;
+  }
+  if ((uint64_t)n_rows + 1 > m->in_row_cap) {
+    m->in_row_cap = 0;
+    if (!em_grow(m->d_in_rows, (uint64_t)n_rows + 1)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    m->in_row_cap = (uint64_t)n_rows + 1;
+  }
+  if (n) HIPCHK(hipMemcpyAsync(m->d_in_res, res, sizeof(grim_subject_result) * (uint64_t)n, hipMemcpyHostToDevice, c->stream), c, -1);
+  if (n_rows) HIPCHK(hipMemcpyAsync(m->d_in_rows, rows, sizeof(grim_row) * (uint64_t)n_rows, hipMemcpyHostToDevice, c->stream), c, -1);
+  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+  return 0;
+}
+
+static bool mt_records_args_ok(grim_match *m, const char *who, const grim_subject_result *res, uint32_t n, const grim_row *rows,
+                               uint32_t n_rows) {
+  if (m->keep_mask == 0 || (m->keep_mask >> GRIM_MAXL) != 0) {
+    set_err(m->ctx, std::string(who) + ": keep_mask is empty or names a locus slot beyond GRIM_MAXL");
+    return false;
+  }
+  if ((n && !res) || (n_rows && !rows) || n_rows > 0x7FFFFFFFu) {
+    set_err(m->ctx, std::string(who) + ": bad arguments");
+    return false;
+  }
+  return true;
+}
+
+extern "C" int grim_match_set_patients(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
+  if (!m) return -1;
+  grim_ctx *c = m->ctx;
+  mt_clear(m);
+  mt_drop_patients(m);
+  if (!mt_records_args_ok(m, "grim_match_set_patients", res, n, rows, n_rows)) return -3;
+  if ((uint64_t)n > GRIM_MATCH_MAX_PAIRS) {
+    set_err(c, "grim_match_set_patients: more patients than GRIM_MATCH_MAX_PAIRS");
+    return -3;
+  }
+  use_device(c->device);
+  if (n) {
+    if (mt_upload(m, "grim_match_set_patients", res, n, rows, n_rows) != 0) return -1;
+    HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MT_S_COUNT * MT_S_SLICES, c->stream), c, -1);
+    if (mt_prepare(m, "grim_match_set_patients", m->P, 0u, m->d_in_res, m->d_in_rows, n, n_rows) != 0) return -1;
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, m->P.first + n, 4, hipMemcpyDeviceToHost, c->stream), c, -1);
+    if (mt_read_stat(m, m->pstat) != 0) return -1;
+    if (total > n_rows) {  // regions that overlap: the kernel left those that did not fit alone
+      mt_drop_patients(m);
+      set_err(c, "grim_match_set_patients: the subjects' genotype rows overlap (more rows than there are)");
+      return -1;
+    }
+  }
+  m->P.n = n;
+  m->have_patients = true;
+  return 0;
+}
+
+// donors (device arrays) against the patients set
+static int mt_run(grim_match *m, const char *who, const grim_subject_result *res, const grim_row *rows, uint32_t n, uint32_t rows_used) {
+  grim_ctx *c = m->ctx;
+  hipStream_t st = c->stream;
+  if (n == 0) return 0;
+  const uint32_t n_p = m->P.n;
+  const uint64_t pairs = (uint64_t)n_p * n;
+  if (pairs + 1 > m->out_cap) {  // never an empty allocation
+    m->out_cap = 0;
+    if (!em_grow(m->d_out, (pairs + 1) * MT_REC)) {
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    m->out_cap = pairs + 1;
+  }
+  HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MT_S_COUNT * MT_S_SLICES, st), c, -1);
+  HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
+  if (mt_prepare(m, who, m->D, 1u, res, rows, n, rows_used) != 0) return -1;
+  if (pairs) {
+    HIPCHK(hipMemsetAsync(m->d_out, 0, sizeof(double) * MT_REC * pairs, st), c, -1);  // a pair that is not computed reads as zero bytes
+    const MtSide P = {m->P.first, m->P.a, m->P.b, m->P.w, m->P.flags}, D = {m->D.first, m->D.a, m->D.b, m->D.w, m->D.flags};
+    for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {  // the grid's second dimension ends at 65535
+      const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+      hipLaunchKernelGGL(mt_pair_kernel, dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, m->keep_mask, m->d_out, m->d_stat);
+    }
+    HIPCHK(hipGetLastError(), c, -1);
+  }
+  HIPCHK(hipEventRecord(m->ev[1], st), c, -1);
+  uint32_t total = 0;
+  uint64_t h[MT_S_COUNT];
+  HIPCHK(hipMemcpyAsync(&total, m->D.first + n, 4, hipMemcpyDeviceToHost, st), c, -1);
+  if (mt_read_stat(m, h) != 0) return -1;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]), c, -1);
+  if (total > rows_used) {
+    set_err(c, std::string(who) + ": the subjects' genotype rows overlap (more rows than there are)");
+    return -1;
+  }
+  m->last_ms = ms;
+  m->n_donors = n;
+  for (int k = 0; k < 8; ++k) m->stat[k] = k < MT_S_COUNT ? h[k] + m->pstat[k] : 0;
+  return 0;
+}
+
+static bool mt_pairs_ok(grim_match *m, const char *who, uint32_t n) {
+  if (!m->have_patients) {
+    set_err(m->ctx, std::string(who) + ": no patients set (call grim_match_set_patients first)");
+    return false;
+  }
+  if ((uint64_t)m->P.n * n > GRIM_MATCH_MAX_PAIRS) {
+    set_err(m->ctx, std::string(who) + ": patients x donors above GRIM_MATCH_MAX_PAIRS");
+    return false;
+  }
+  return true;
+}
+
+extern "C" int grim_match_run(grim_match *m, grim_batch *b) {
+  if (!m || !b) return -1;
+  grim_ctx *c = m->ctx;
+  mt_clear(m);
+  if (b->ctx != c) {
+    set_err(c, "grim_match_run: the batch belongs to another context");
+    return -3;
+  }
+  if (!b->ran_ok) {
+    set_err(c, "grim_match_run: the batch holds no finished run (call grim_batch_run first)");
+    return -3;
+  }
+  if (!b->a.prm.out_muug) {
+    set_err(c, "grim_match_run: the batch was built with out_muug off: it holds no genotype rows");
+    return -3;
+  }
+  if (m->keep_mask == 0 || b->g->d.n_loci > GRIM_MAXL || (m->keep_mask >> b->g->d.n_loci) != 0) {
+    set_err(c, "grim_match_run: keep_mask is empty or names a locus slot the graph does not have");
+    return -3;
+  }
+  if (!mt_pairs_ok(m, "grim_match_run", b->n_subj)) return -3;
+  use_device(c->device);
+  return mt_run(m, "grim_match_run", b->a.res, b->a.rows, b->n_subj, b->rows_used);
+}
+
+extern "C" int grim_match_run_records(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
+  if (!m) return -1;
+  mt_clear(m);
+  if (!mt_records_args_ok(m, "grim_match_run_records", res, n, rows, n_rows)) return -3;
+  if (!mt_pairs_ok(m, "grim_match_run_records", n)) return -3;
+  use_device(m->ctx->device);
+  if (n == 0) return 0;
+  if (mt_upload(m, "grim_match_run_records", res, n, rows, n_rows) != 0) return -1;
+  return mt_run(m, "grim_match_run_records", m->d_in_res, m->d_in_rows, n, n_rows);
+}
+
+extern "C" uint32_t grim_match_patients(const grim_match *m) { return m ? m->P.n : 0; }
+extern "C" uint32_t grim_match_donors(const grim_match *m) { return m ? m->n_donors : 0; }
+extern "C" double grim_match_kernel_ms(const grim_match *m) { return m ? m->last_ms : 0.0; }
+
+extern "C" int grim_match_results(grim_match *m, grim_match_rec *out, uint8_t *patient_flags, uint8_t *donor_flags) {
+  if (!m) return -1;
+  grim_ctx *c = m->ctx;
+  use_device(c->device);
+  const uint64_t pairs = (uint64_t)m->P.n * m->n_donors;
+  if (out && pairs) HIPCHK(hipMemcpy(out, m->d_out, sizeof(grim_match_rec) * pairs, hipMemcpyDeviceToHost), c, -1);
+  if (patient_flags && m->P.n) HIPCHK(hipMemcpy(patient_flags, m->P.flags, m->P.n, hipMemcpyDeviceToHost), c, -1);
+  if (donor_flags && m->n_donors) HIPCHK(hipMemcpy(donor_flags, m->D.flags, m->n_donors, hipMemcpyDeviceToHost), c, -1);
+  return 0;
+}
+
+extern "C" int grim_match_stats(const grim_match *m, uint64_t out[8]) {
+  if (!m || !out) return -1;
+  for (int k = 0; k < 8; ++k) out[k] = m->stat[k];
   return 0;
 }

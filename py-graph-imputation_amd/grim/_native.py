@@ -509,6 +509,124 @@ class MarginalReducer:
             pass
 
 
+# ---- match probabilities (grim_match_*): the UMUG rows of patients against those of finished batches of donors ----
+EXPORTS += [
+    "grim_match_create", "grim_match_set_patients", "grim_match_run", "grim_match_run_records", "grim_match_patients",
+    "grim_match_donors", "grim_match_results", "grim_match_stats", "grim_match_kernel_ms", "grim_match_free",
+]
+
+MATCH_DT = np.dtype([("mm", "<f8", (2 * MAXL + 1,)), ("locus", "<f8", (MAXL,))])
+assert MATCH_DT.itemsize == 128
+MATCH_STATS = ("patients_valid", "donors_valid", "patients_private", "donors_private", "undefined", "pairs", "row_pairs")
+MATCH_VALID, MATCH_PRIVATE, MATCH_UNDEFINED = 1, 2, 4
+MATCH_MAX_PAIRS = 1 << 24
+
+_match_ready = False
+
+
+def _match_lib():
+    global _match_ready
+    L = lib()
+    if not _match_ready:
+        L.grim_match_create.restype = C.c_void_p
+        L.grim_match_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.grim_match_set_patients.restype = C.c_int
+        L.grim_match_set_patients.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.grim_match_run.restype = C.c_int
+        L.grim_match_run.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_match_run_records.restype = C.c_int
+        L.grim_match_run_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.grim_match_patients.restype = C.c_uint32
+        L.grim_match_patients.argtypes = [C.c_void_p]
+        L.grim_match_donors.restype = C.c_uint32
+        L.grim_match_donors.argtypes = [C.c_void_p]
+        L.grim_match_results.restype = C.c_int
+        L.grim_match_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_match_stats.restype = C.c_int
+        L.grim_match_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        L.grim_match_kernel_ms.restype = C.c_double
+        L.grim_match_kernel_ms.argtypes = [C.c_void_p]
+        L.grim_match_free.argtypes = [C.c_void_p]
+        _match_ready = True
+    return L
+
+
+class Matcher:
+    """grim_match: for every (patient, donor) pair the probabilities of 0, 1, 2, ... mismatching alleles over the kept locus
+    slots and the per-locus match probabilities, on the device (include/grim_hip.h, the grim_match_* block).  The patients
+    stay set across runs; results(), stats() and kernel_ms() speak of the last run."""
+
+    def __init__(self, ctx, keep_mask, n_alleles):
+        L = _match_lib()
+        self.ctx = ctx
+        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
+        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        self.h = L.grim_match_create(ctx.h, int(keep_mask), arr)
+        if not self.h:
+            raise NativeError("grim_match_create failed: " + ctx.error())
+
+    @staticmethod
+    def _records(res, rows):
+        res = np.ascontiguousarray(res, dtype=RESULT_DT)
+        rows = np.ascontiguousarray(rows, dtype=ROW_DT)
+        return res, rows, (_ptr(res) if res.size else None, res.shape[0], _ptr(rows) if rows.size else None, rows.shape[0])
+
+    def set_patients(self, res, rows):
+        """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows"""
+        res, rows, args = self._records(res, rows)
+        rc = _match_lib().grim_match_set_patients(self.h, *args)
+        if rc != 0:
+            raise NativeError("grim_match_set_patients failed (%d): %s" % (rc, self.ctx.error()))
+
+    def run(self, batch):
+        """one DeviceBatch after its run() as donors, where its rows lie; synchronous"""
+        rc = _match_lib().grim_match_run(self.h, batch.h)
+        if rc != 0:
+            raise NativeError("grim_match_run failed (%d): %s" % (rc, self.ctx.error()))
+
+    def run_records(self, res, rows):
+        """host records as donors, through the same kernels"""
+        res, rows, args = self._records(res, rows)
+        rc = _match_lib().grim_match_run_records(self.h, *args)
+        if rc != 0:
+            raise NativeError("grim_match_run_records failed (%d): %s" % (rc, self.ctx.error()))
+
+    def patients(self):
+        return int(_match_lib().grim_match_patients(self.h))
+
+    def donors(self):
+        return int(_match_lib().grim_match_donors(self.h))
+
+    def results(self):
+        """-> (records MATCH_DT[patients][donors], patient flags u8[patients], donor flags u8[donors])"""
+        n_p, n_d = self.patients(), self.donors()
+        out = np.zeros((n_p, n_d), dtype=MATCH_DT)
+        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
+        if _match_lib().grim_match_results(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
+                                           _ptr(df) if n_d else None) != 0:
+            raise NativeError("grim_match_results failed: " + self.ctx.error())
+        return out, pf, df
+
+    def stats(self):
+        out = (C.c_uint64 * 8)()
+        _match_lib().grim_match_stats(self.h, out)
+        return {k: int(v) for k, v in zip(MATCH_STATS, out)}
+
+    def kernel_ms(self):
+        return float(_match_lib().grim_match_kernel_ms(self.h))
+
+    def close(self):
+        if self.h:
+            _match_lib().grim_match_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ======================================================================================================
 # host-side helpers of the library (C++: allele dictionary, tokenizer, formatter) -- no GPU needed
 # ======================================================================================================

@@ -1,0 +1,453 @@
+"""
+Match probabilities between imputed subjects: for a patient and a donor, the probability that their genotypes differ in
+0, 1, 2, ... alleles over a set K of kept loci (a 10/10, a 9/10, an 8/8 match), and per locus the probability of no mismatch.
+
+The reference ends at the printed `.umug` files; the operation is defined here:
+
+    per subject, genotype rows k = 0..n-1 in rank order with probabilities p_k:
+      total = ((p_0 + p_1) + p_2) + ...,  w_k = p_k / total
+    per row pair (patient row i, donor row j), per kept locus with the patient's alleles x1, x2 and the donor's y1, y2:
+      eq(x, y) = x == y and x is typed          (an untyped locus equals nothing)
+      mm = 2 - max(eq(x1,y1) + eq(x2,y2), eq(x1,y2) + eq(x2,y1));   M(i,j) = the sum of mm over the kept loci
+    per (patient, donor) pair, with w the patient's weights and v the donor's:
+      for j (donor rows, rank order):
+          ph[*] = 0.0, pl[*] = 0.0
+          for i (patient rows, rank order):  t = w_i * v_j;  ph[M(i,j)] += t;  pl[locus] += t for every locus with mm == 0
+          H[m] += ph[m],  L[locus] += pl[locus]
+      mm[m] = H[m],  locus[s] = L[s]
+
+`match_probabilities` runs it on the device, on the rows the donors' batches leave in HBM (csrc/grim_match.h).  Pairs in
+which a subject holds an allele the dictionary does not know are left out by the device (the allele's id is private to the
+subject) and folded here on allele text.  `match_records` is the same fold over record arrays in plain Python floats, laid
+out as the device lays it out; `match_umug_text` the same over `.umug` text.  The three agree bit for bit.  There is no CPU
+fallback of the device functions.
+"""
+
+import math
+import os
+
+import numpy as np
+
+from . import _native as nat
+from .marginal import keep_mask as _keep_mask
+
+
+class _Folder:
+    """the pair fold on row genotypes: a row genotype is a tuple with one (x, y) allele pair per kept locus (None = untyped);
+    alleles compare with ==.  Alleles are numbered (0 = untyped) so that the mismatch COUNTS of all row pairs come from integer
+    array compares; every floating-point operation is a plain Python one, in the contract's order."""
+
+    def __init__(self, nk):
+        self.nk = nk
+        self.ids = {None: 0}
+
+    def pack(self, genos):
+        """[row genotype] -> (x[nk][rows], y[nk][rows]) allele numbers"""
+        ids = self.ids
+        x = np.zeros((self.nk, len(genos)), dtype=np.int64)
+        y = np.zeros((self.nk, len(genos)), dtype=np.int64)
+        for r, geno in enumerate(genos):
+            for k, (a, b) in enumerate(geno):
+                x[k, r] = ids.setdefault(a, len(ids))
+                y[k, r] = ids.setdefault(b, len(ids))
+        return x, y
+
+    def fold(self, pg, pw, dg, dv):
+        """patient rows (packed genotypes pg, weights pw) against donor rows (dg, dv) -> (H[2 nk + 1], L[nk])"""
+        nk = self.nk
+        nb = 2 * nk + 1
+        n_p, n_d = len(pw), len(dv)
+        M = np.zeros((n_d, n_p), dtype=np.int64)  # M[j][i]
+        zero = []  # per kept locus and donor row: the patient rows without a mismatch there, ascending
+        for k in range(nk):
+            x1, x2, y1, y2 = pg[0][k][None, :], pg[1][k][None, :], dg[0][k][:, None], dg[1][k][:, None]
+            straight = ((x1 == y1) & (x1 != 0)).astype(np.int64) + ((x2 == y2) & (x2 != 0))
+            crossed = ((x1 == y2) & (x1 != 0)).astype(np.int64) + ((x2 == y1) & (x2 != 0))
+            mm = 2 - np.maximum(straight, crossed)
+            M += mm
+            jj, ii = np.nonzero(mm == 0)
+            zero.append((np.searchsorted(jj, np.arange(n_d + 1)).tolist(), ii.tolist()))
+        M = M.tolist()
+        H, L = [0.0] * nb, [0.0] * nk
+        for j in range(n_d):
+            v = dv[j]
+            ts = [w * v for w in pw]
+            ph = [0.0] * nb
+            for m, t in zip(M[j], ts):
+                ph[m] = ph[m] + t
+            for m in range(nb):
+                H[m] = H[m] + ph[m]
+            for k in range(nk):
+                bounds, ii = zero[k]
+                pl = 0.0
+                for i in ii[bounds[j]:bounds[j + 1]]:
+                    pl = pl + ts[i]
+                L[k] = L[k] + pl
+        return H, L
+
+
+def _total(ps):
+    total = ps[0]
+    for p in ps[1:]:
+        total = total + p
+    return total
+
+
+def _slots_of(keep_mask):
+    keep_mask = int(keep_mask)
+    if keep_mask <= 0 or keep_mask >> nat.MAXL:
+        raise ValueError("keep_mask is empty or names a locus slot beyond %d" % nat.MAXL)
+    return [s for s in range(nat.MAXL) if (keep_mask >> s) & 1]
+
+
+def _store(rec, slots, H, L):
+    """H, L of a pair into one nat.MATCH_DT record"""
+    rec["mm"][:len(H)] = H
+    for k, s in enumerate(slots):
+        rec["locus"][s] = L[k]
+
+
+def _side(res, rows, slots, n_alleles, folder):
+    """one side's subjects as the device prepares them -> (flags, [(packed genotypes, weights) or None])"""
+    m = len(rows)
+    flags = np.zeros(len(res), dtype=np.uint8)
+    subs = []
+    used = 0
+    for i, r in enumerate(res):
+        n, off = int(r["n_rows"][nat.T_UMUG]), int(r["row_off"][nat.T_UMUG])
+        if int(r["status"]) != nat.ST_OK or n == 0 or off > m or n > m - off:
+            subs.append(None)
+            continue
+        used += n
+        ps = [float(rows[off + k]["prob"]) for k in range(n)]
+        total = _total(ps)
+        valid = math.isfinite(total) and total > 0.0
+        private = undefined = False
+        genos = []
+        for k in range(n):
+            a, b = int(rows[off + k]["a"]), int(rows[off + k]["b"])
+            fa = [(a >> (nat.ABITS * s)) & 0xFFF for s in range(nat.MAXL)]
+            fb = [(b >> (nat.ABITS * s)) & 0xFFF for s in range(nat.MAXL)]
+            undefined |= any((x == 0) != (y == 0) for x, y in zip(fa, fb))
+            private |= any(fa[s] > n_alleles[s] or fb[s] > n_alleles[s] for s in slots)
+            genos.append(tuple((fa[s] or None, fb[s] or None) for s in slots))
+        flags[i] = (nat.MATCH_VALID if valid else 0) | (nat.MATCH_PRIVATE if private else 0) | (nat.MATCH_UNDEFINED if undefined else 0)
+        subs.append((folder.pack(genos), [p / total for p in ps]) if valid else None)
+    if used > m:
+        raise ValueError("the subjects' genotype rows overlap (more rows than there are)")
+    return flags, subs
+
+
+def match_records(pres, prows, dres, drows, keep_mask, n_alleles):
+    """The fold on record arrays (nat.RESULT_DT / nat.ROW_DT of the patients and of the donors) as grim_match_run_records
+    defines it (include/grim_hip.h) -> (records nat.MATCH_DT[P][D], patient flags, donor flags, stats), laid out as the device
+    lays them out: a pair that is not computed is a record of zeros; without donors every statistic is 0."""
+    slots = _slots_of(keep_mask)
+    n_alleles = [int(x) for x in n_alleles] + [0] * (nat.MAXL - len(n_alleles))
+    folder = _Folder(len(slots))
+    pflags, psubs = _side(pres, prows, slots, n_alleles, folder)
+    dflags, dsubs = _side(dres, drows, slots, n_alleles, folder)
+    out = np.zeros((len(pres), len(dres)), dtype=nat.MATCH_DT)
+    stats = dict.fromkeys(nat.MATCH_STATS, 0)
+    if len(dres) == 0:
+        return out, pflags, dflags, stats
+    for side, flags in (("patients", pflags), ("donors", dflags)):
+        stats[side + "_valid"] = int(np.count_nonzero(flags & nat.MATCH_VALID))
+        stats[side + "_private"] = int(np.count_nonzero(flags & nat.MATCH_PRIVATE))
+        stats["undefined"] += int(np.count_nonzero(flags & nat.MATCH_UNDEFINED))
+    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
+    for p, ps in enumerate(psubs):
+        if (pflags[p] & ready) != nat.MATCH_VALID:
+            continue
+        for d, ds in enumerate(dsubs):
+            if (dflags[d] & ready) != nat.MATCH_VALID:
+                continue
+            H, L = folder.fold(ps[0], ps[1], ds[0], ds[1])
+            _store(out[p, d], slots, H, L)
+            stats["pairs"] += 1
+            stats["row_pairs"] += len(ps[1]) * len(ds[1])
+    return out, pflags, dflags, stats
+
+
+def _text_subjects(text, keep):
+    """`.umug` text -> [(id, [({locus: (x, y)}, p)])]: a subject is the run of rows from one rank 0 to the next"""
+    subs = []
+    sid = None
+    for line in text.splitlines():
+        if not line:
+            continue
+        f = line.split(",")
+        if len(f) != 4:
+            raise ValueError("not an id,genotype,probability,rank row: %r" % line)
+        if int(f[3]) == 0 or f[0] != sid:
+            sid = f[0]
+            subs.append((sid, []))
+        if int(f[3]) != len(subs[-1][1]):
+            raise ValueError("ranks of subject %s are not 0..n-1" % f[0])
+        geno = {}
+        for part in f[1].split("^"):
+            if not part:
+                continue
+            name = part.split("*", 1)[0]
+            if name not in keep:
+                continue
+            pair = part.split("+")
+            if len(pair) != 2:
+                raise ValueError("not two alleles at locus %s: %r" % (name, line))
+            geno[name] = (pair[0], pair[1])
+        subs[-1][1].append((geno, float(f[2])))
+    return subs
+
+
+def match_umug_text(patient_text, donor_text, keep_loci, loci=None):
+    """The fold on `.umug` text in `id,genotype,p,rank` form -> (patient ids, donor ids, records[P][D]); a record is
+    (mm[0..2|K|], {locus name: probability of no mismatch}).  A subject is the run of rows from one rank 0 to the next; a
+    `^`-part of a genotype belongs to the locus named before its first `*`, its two alleles are the `+`-separated texts; a
+    kept locus a row lacks is untyped; two alleles are equal when their texts are.  `loci`: the names that may be kept (an
+    unknown one raises)."""
+    keep = [keep_loci] if isinstance(keep_loci, str) else list(dict.fromkeys(keep_loci))
+    if not keep:
+        raise ValueError("keep_loci is empty")
+    if loci is not None:
+        _keep_mask({name: 0 for name in loci}, keep)
+    folder = _Folder(len(keep))
+    sides = []
+    for text in (patient_text, donor_text):
+        side = []
+        for sid, rows in _text_subjects(text, set(keep)):
+            total = _total([p for _, p in rows])
+            if not (math.isfinite(total) and total > 0.0):
+                raise ValueError("genotype rows of subject %s whose probabilities add up to %r" % (sid, total))
+            genos = folder.pack([tuple(g.get(name, (None, None)) for name in keep) for g, _ in rows])
+            side.append((sid, genos, [p / total for _, p in rows]))
+        sides.append(side)
+    records = []
+    for _, pg, pw in sides[0]:
+        line = []
+        for _, dg, dv in sides[1]:
+            H, L = folder.fold(pg, pw, dg, dv)
+            line.append((H, dict(zip(keep, L))))
+        records.append(line)
+    return [s[0] for s in sides[0]], [s[0] for s in sides[1]], records
+
+
+def text_records_array(records, locus_slot):
+    """records of match_umug_text -> nat.MATCH_DT[P][D]; `locus_slot`: name -> slot (Graph.locus_slot)"""
+    out = np.zeros((len(records), len(records[0]) if records else 0), dtype=nat.MATCH_DT)
+    for p, line in enumerate(records):
+        for d, (H, L) in enumerate(line):
+            out[p, d]["mm"][:len(H)] = H
+            for name, v in L.items():
+                out[p, d]["locus"][int(locus_slot[name])] = v
+    return out
+
+
+class _Block:
+    """a block of input lines tokenised and imputed as one device batch (genotype output on); the caller closes it"""
+
+    def __init__(self, imputation, ctx, dgraph, params, ps, lines, lo, planb):
+        g = imputation.netGraph
+        pops = imputation.populations
+        host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
+        self.lo = lo
+        self.batch = None
+        self.parsed = nat.Parsed(g.adict, "".join(l + "\n" for l in lines).encode(), planb)
+        try:
+            kinds = self.parsed.kinds()
+            dev = self.parsed.dev_index()
+            self.bad = [(lo + int(j), self.parsed.subject_id(int(j)), host_reason[int(kinds[j])])
+                        for j in np.flatnonzero(np.isin(kinds, list(host_reason)))]
+            on_dev = np.flatnonzero(kinds == nat.K_DEVICE)
+            self.line_of = np.zeros(self.parsed.n_subjects, dtype=np.int64)  # device subject -> line of the block
+            self.line_of[dev[on_dev]] = on_dev
+            subj = self.parsed.subjects()
+            if len(subj):
+                races = self.parsed.races()
+                priors = np.ones((max(1, len(races)), len(pops), len(pops)))
+                for k, (r1, r2) in enumerate(races):
+                    priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+                self.batch = nat.DeviceBatch(ctx, dgraph, params, subj, self.parsed.tokens(), priors)
+                self.batch.run()
+        except BaseException:
+            self.close()
+            raise
+        self._records = None
+
+    def records(self):
+        if self._records is None:
+            self._records = self.batch.results()
+        return self._records
+
+    def unsupported(self):
+        res, _ = self.records()
+        return [(self.lo + int(self.line_of[i]), self.parsed.subject_id(int(self.line_of[i])), int(res[i]["reason"]))
+                for i in np.flatnonzero(res["status"] == nat.ST_UNSUPPORTED)]
+
+    def text_subject(self, g, i, slots, n_alleles, folder):
+        """device subject i's rows on allele text -> (packed genotypes, weights)"""
+        res, rows = self.records()
+        n, off = int(res[i]["n_rows"][nat.T_UMUG]), int(res[i]["row_off"][nat.T_UMUG])
+        line = int(self.line_of[i])
+        names = {}
+
+        def text(s, f):
+            if f == 0:
+                return None
+            if (s, f) not in names:  # an id above the dictionary's is the line's own
+                names[(s, f)] = self.parsed.allele(line, s, f - 1) if f > n_alleles[s] else g.key_alleles(f << (nat.ABITS * s))[s]
+            return names[(s, f)]
+
+        ps = [float(rows[off + k]["prob"]) for k in range(n)]
+        total = _total(ps)
+        genos = []
+        for k in range(n):
+            a, b = int(rows[off + k]["a"]), int(rows[off + k]["b"])
+            genos.append(tuple((text(s, (a >> (nat.ABITS * s)) & 0xFFF), text(s, (b >> (nat.ABITS * s)) & 0xFFF)) for s in slots))
+        return folder.pack(genos), [p / total for p in ps]
+
+    def close(self):
+        if self.batch is not None:
+            self.batch.close()
+            self.batch = None
+        self.parsed.close()
+
+
+def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines=65536, planb=None, em=False):
+    """Match probabilities of every patient against every donor on the device.  `patient_lines`: input lines;
+    `donor_lines_or_path`: input lines (a list) or the path of an input file; `config`: the configuration dict of
+    `load_config`; `keep_loci`: locus names of its loci_map.  The patients are imputed as one device batch, their records
+    fetched and set once; the donors are cut into blocks of `block_lines` lines (lowered so that patients x block stays within
+    GRIM_MATCH_MAX_PAIRS), each tokenised, imputed as one device batch (genotype output on, the rest as configured) and matched
+    where its rows lie.  Pairs the device leaves out because a subject holds an allele the dictionary does not know are folded
+    here on allele text.  -> (patient_ok, donor_ok, records, stats): records is nat.MATCH_DT[len(patient_lines)][len(donor
+    lines)], zero for lines without genotype rows; *_ok say which lines have them; stats adds `blocks`, `kernel_ms` and
+    `host_pairs` (pairs folded on text).  The cuts do not show in any byte.  Subjects the device cannot answer follow
+    `imputation.on_unsupported` as in `impute_lines_block`."""
+    from .imputation.impute import UnsupportedSubjects
+
+    g = imputation.netGraph
+    mask = _keep_mask(g.locus_slot, keep_loci)
+    slots = _slots_of(mask)
+    if isinstance(donor_lines_or_path, (str, bytes, os.PathLike)):
+        with open(donor_lines_or_path) as fh:
+            dlines = fh.read().splitlines()
+    else:
+        dlines = [l.rstrip("\n") for l in donor_lines_or_path]
+    plines = [l.rstrip("\n") for l in patient_lines]
+    if len(plines) > nat.MATCH_MAX_PAIRS:
+        raise ValueError("%d patients: more than %d pairs with a single donor" % (len(plines), nat.MATCH_MAX_PAIRS))
+    if planb is None:
+        planb = config["planb"]
+    block_lines = max(1, min(int(block_lines), nat.MATCH_MAX_PAIRS // max(1, len(plines))))
+    cfg = dict(config, output_MUUG=True)
+    params = imputation._params(cfg, planb, False, em)
+    ps, _ = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
+    ctx = nat.default_context(imputation.device)
+    dgraph = g.device(ctx)
+    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))] + [0] * (nat.MAXL - len(g.full_loci))
+    matcher = nat.Matcher(ctx, mask, n_alleles)
+    imputation.unsupported = []
+    stats = dict.fromkeys(nat.MATCH_STATS, 0)
+    stats.update(blocks=0, kernel_ms=0.0, host_pairs=0)
+    out = np.zeros((len(plines), len(dlines)), dtype=nat.MATCH_DT)
+    patient_ok, donor_ok = np.zeros(len(plines), dtype=bool), np.zeros(len(dlines), dtype=bool)
+    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
+    folder = _Folder(len(slots))  # of the text route
+    pblock = None
+
+    def check(block, flags):
+        bad = block.bad + (block.unsupported() if block.batch is not None and not flags.all() else [])
+        imputation.unsupported += sorted(bad)
+        if imputation.unsupported and imputation.on_unsupported == "raise":
+            raise UnsupportedSubjects(imputation.unsupported)
+        if np.count_nonzero(flags & nat.MATCH_UNDEFINED):
+            raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their match is "
+                             "not defined" % np.count_nonzero(flags & nat.MATCH_UNDEFINED))
+
+    try:
+        pblock = _Block(imputation, ctx, dgraph, params, ps, plines, 0, planb)
+        pf = np.zeros(0, dtype=np.uint8)
+        if pblock.batch is not None:
+            matcher.set_patients(*pblock.records())
+            pf = matcher.results()[1]
+            pblock.batch.close()  # the records are on the host, the patients prepared on the device
+        check(pblock, pf)
+        patient_ok[pblock.line_of[np.flatnonzero(pf & nat.MATCH_VALID)]] = True
+        stats["patients_valid"] = int(np.count_nonzero(pf & nat.MATCH_VALID))
+        stats["patients_private"] = int(np.count_nonzero(pf & nat.MATCH_PRIVATE))
+        ptext = {}  # patient -> its rows on allele text
+        for lo in range(0, len(dlines), block_lines):
+            block = _Block(imputation, ctx, dgraph, params, ps, dlines[lo:lo + block_lines], lo, planb)
+            try:
+                if block.batch is None:
+                    check(block, np.zeros(0, dtype=np.uint8))
+                    continue
+                matcher.run(block.batch)
+                rec, _, df = matcher.results()
+                run = matcher.stats()
+                check(block, df)
+                for k in ("donors_valid", "donors_private", "pairs", "row_pairs"):
+                    stats[k] += run[k]
+                stats["kernel_ms"] += matcher.kernel_ms()
+                stats["blocks"] += 1
+                donor_ok[lo + block.line_of[np.flatnonzero(df & nat.MATCH_VALID)]] = True
+                # pairs the device left out for a private allele: the same fold on allele text
+                dtext = {}
+                for p in np.flatnonzero(pf & nat.MATCH_VALID):
+                    for d in np.flatnonzero(df & nat.MATCH_VALID):
+                        if (pf[p] & ready) == nat.MATCH_VALID and (df[d] & ready) == nat.MATCH_VALID:
+                            continue
+                        if p not in ptext:
+                            ptext[p] = pblock.text_subject(g, int(p), slots, n_alleles, folder)
+                        if d not in dtext:
+                            dtext[d] = block.text_subject(g, int(d), slots, n_alleles, folder)
+                        H, L = folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
+                        _store(rec[p, d], slots, H, L)
+                        stats["host_pairs"] += 1
+                if len(pf):
+                    out[pblock.line_of[:, None], lo + block.line_of[None, :]] = rec
+            finally:
+                block.close()
+    finally:
+        if pblock is not None:
+            pblock.close()
+        matcher.close()
+    return patient_ok, donor_ok, out, stats
+
+
+def line_id(line):
+    """the subject id of an input line as the tokenizer takes it: the field before the first ',' when the line has one, else
+    before the first '%' (impute.py:2024-2027)"""
+    return line.split("," if "," in line else "%", 1)[0]
+
+
+def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0=0.0, block_lines=65536):
+    """The configuration's input file as donors against the input file `patients_path`, on `graph` (built from the
+    configuration's graph CSVs when None) -> a CSV at `out_path`: a header `patient_id,donor_id,mm0,...,mm{2|K|},<kept locus
+    names>`, then one line per computed pair with mm0 >= min_p0, patient-major, floats written with repr.  Paths are taken
+    as the configuration gives them.  -> stats"""
+    from .grim import graph_instance
+    from .imputation.impute import Imputation
+    from .run_impute_def import load_config
+
+    config, _ = load_config(conf_file)
+    if graph is None:
+        graph = graph_instance(config)
+    imp = Imputation(graph, config)
+    with open(patients_path) as fh:
+        plines = fh.read().splitlines()
+    with open(config["imputation_input_file"]) as fh:
+        dlines = fh.read().splitlines()
+    pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines)
+    slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
+    nb = 2 * len(slots) + 1
+    pid, did = [line_id(l) for l in plines], [line_id(l) for l in dlines]
+    with open(out_path, "w") as fh:
+        fh.write(",".join(["patient_id", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots]) + "\n")
+        for p in np.flatnonzero(pok):
+            for d in np.flatnonzero(dok):
+                r = rec[p, d]
+                if float(r["mm"][0]) >= min_p0:
+                    vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
+                    fh.write("%s,%s,%s\n" % (pid[p], did[d], ",".join(repr(v) for v in vals)))
+    return stats
