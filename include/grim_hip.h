@@ -555,6 +555,63 @@ int grim_match_stats(const grim_match *m, uint64_t out[8]);
 double grim_match_kernel_ms(const grim_match *m);
 void grim_match_free(grim_match *m);
 
+/* ======================= donor search: each patient's best N donors (csrc/grim_search.h) ================================
+ * The match records above, computed run by run, and on the device a selection of every patient's first top_n donors over all
+ * runs: only patients x top_n hits come down, once, however many donor runs were streamed.
+ * Inputs: those of the match block (keep_mask, n_alleles, patients set once, donors in any number of runs), and
+ *   top_n in 1..GRIM_SEARCH_MAX_N; a threshold min_p0, a double that is not NaN; per run one uint32_t id per donor, distinct
+ *   over the whole search and the caller's own.
+ * Candidates: a pair (p, d) is a candidate iff it is computed (both subjects GRIM_MATCH_VALID, neither GRIM_MATCH_PRIVATE;
+ *   decided from the flags, not from the record's bytes) and rec.mm[0] >= min_p0.  Every mm value of a computed pair is finite
+ *   and >= +0.0, so plain > and == on doubles are a total preorder: there is no NaN to handle.
+ * Order: candidate x comes before candidate y iff x.mm[0] > y.mm[0]; or the mm[0] are equal and x.mm[1] > y.mm[1] (mm[1]
+ *   always exists, 2|K| >= 2); or both are equal and x.id < y.id.  Ids are distinct, so the order is strict: the answer does
+ *   not depend on how the selection is done, on tile size, on block cuts or on the order of the runs.  No floating-point
+ *   operation is added: the records are the match block's, bit for bit.
+ * Result per patient: a count n_hits <= top_n and top_n slots of grim_search_hit.  The first n_hits slots hold the first
+ *   candidates in that order over all runs since the patients were set or the search was reset; the other slots are donor =
+ *   GRIM_SEARCH_NO_DONOR with a zero record.  Results are patient-major: hits[p * top_n + k].
+ * Statistics: the match block's seven counters, each run's summed, and [7] candidates: the pairs that passed the threshold,
+ *   counted as u64 on the device.
+ * Environment, read when a search is created: GRIM_SEARCH_TILE=n, the entries a workgroup sorts at a time, a power of two with
+ *   2 top_n <= n <= GRIM_SEARCH_TILE_MAX (the default); for tests: small tiles make deep reduction trees on small inputs. */
+#define GRIM_SEARCH_MAX_N 256u
+#define GRIM_SEARCH_TILE_MAX 2048u
+#define GRIM_SEARCH_NO_DONOR 0xFFFFFFFFu
+typedef struct {
+  uint32_t donor;    /* the donor's id as the caller gave it */
+  uint32_t reserved; /* 0 */
+  grim_match_rec rec;
+} grim_search_hit; /* 136 bytes */
+typedef struct grim_search grim_search;
+/* NULL with a grim_last_error text when top_n is 0 or above GRIM_SEARCH_MAX_N, min_p0 is NaN or GRIM_SEARCH_TILE is not as
+ * above */
+grim_search *grim_search_create(grim_ctx *ctx, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n, double min_p0);
+/* as grim_match_set_patients; also empties the hit lists and the summed statistics */
+int grim_search_set_patients(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows);
+/* empties the hit lists and the summed statistics; the patients stay */
+int grim_search_reset(grim_search *s);
+/* the subjects of a finished batch as donors, donor_ids[subjects of the batch] (host memory); synchronous.  Answers -3 with a
+ * text when donor_ids is null with donors, and with the matcher's own text whenever the match block refuses.  A refused or
+ * failed run adds nothing: the hit lists and the summed statistics are what they were before it. */
+int grim_search_run(grim_search *s, grim_batch *donors, const uint32_t *donor_ids);
+/* the same with donors given as host records, donor_ids[n] */
+int grim_search_run_records(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows,
+                            const uint32_t *donor_ids);
+/* hits[patients * top_n], n_hits[patients], over all runs so far; a null pointer skips that part */
+int grim_search_results(grim_search *s, grim_search_hit *hits, uint32_t *n_hits);
+/* patient_flags[patients], donor_flags[donors of the last run]; a null pointer skips that part */
+int grim_search_flags(grim_search *s, uint8_t *patient_flags, uint8_t *donor_flags);
+uint32_t grim_search_patients(const grim_search *s); /* as set */
+uint32_t grim_search_donors(const grim_search *s);   /* of the last run */
+uint32_t grim_search_top_n(const grim_search *s);
+int grim_search_stats(const grim_search *s, uint64_t out[8]);
+/* device time of the last run: the match block's kernels plus the selection */
+double grim_search_kernel_ms(const grim_search *s);
+/* device time of the last run's selection kernels alone, between their own start/stop events */
+double grim_search_select_ms(const grim_search *s);
+void grim_search_free(grim_search *s);
+
 #ifdef __cplusplus
 }
 #endif

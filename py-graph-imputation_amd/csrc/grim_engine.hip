@@ -24,6 +24,7 @@
 #include "grim_em.h"
 #include "grim_marginal.h"
 #include "grim_match.h"
+#include "grim_search.h"
 #include "grim_engine_internal.h"
 #include "grim_host_internal.h"
 #include "grim_sdma.h"
@@ -2550,5 +2551,254 @@ extern "C" int grim_match_results(grim_match *m, grim_match_rec *out, uint8_t *p
 extern "C" int grim_match_stats(const grim_match *m, uint64_t out[8]) {
   if (!m || !out) return -1;
   for (int k = 0; k < 8; ++k) out[k] = m->stat[k];
+  return 0;
+}
+
+// =================================================================================================
+// Donor search (grim_search.h): each patient's best top_n donors over any number of runs, selected on the device from the
+// records the matcher's pair kernel leaves in its result buffer
+// =================================================================================================
+struct grim_search {
+  grim_ctx *ctx;
+  grim_match *m;  // owned; driven through the grim_match_* doors, whose behaviour is theirs
+  uint32_t top_n, tile;
+  double min_p0;
+  uint32_t *d_ids;
+  uint64_t ids_cap;
+  SrKey *d_keys[2];  // the lists of a level and of the next, in turns
+  uint32_t *d_cnt[2];
+  uint64_t keys_cap, cnt_cap;  // lists of top_n keys; counts
+  // the running list, double-buffered: run r reads [cur] and writes [cur ^ 1]
+  SrHit *d_hits[2];
+  SrKey *d_run_keys[2];
+  uint32_t *d_run_cnt[2];
+  uint64_t run_cap;  // patients
+  int cur;
+  bool have_running;  // [cur] holds lists (false: every list is empty, nothing on the device says so)
+  unsigned long long *d_cand;
+  uint64_t sum[8];  // the matcher's seven counters summed over the runs, [7] candidates
+  hipEvent_t ev[2];
+  double select_ms, kernel_ms;  // of the last run
+};
+
+static void sr_empty(grim_search *s) {
+  s->have_running = false;
+  for (uint64_t &x : s->sum) x = 0;
+  s->select_ms = s->kernel_ms = 0.0;
+}
+
+extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n,
+                                           double min_p0) {
+  if (!c || !n_alleles) {
+    set_err(c, "grim_search_create: bad arguments");
+    return nullptr;
+  }
+  if (top_n == 0 || top_n > GRIM_SEARCH_MAX_N) {
+    set_err(c, "grim_search_create: top_n must be 1.." + std::to_string(GRIM_SEARCH_MAX_N));
+    return nullptr;
+  }
+  if (min_p0 != min_p0) {
+    set_err(c, "grim_search_create: min_p0 is not a number");
+    return nullptr;
+  }
+  uint32_t tile = SR_TILE;
+  if (const char *e = getenv("GRIM_SEARCH_TILE")) {  // for tests: small tiles make deep trees on small inputs
+    char *end = nullptr;
+    const unsigned long long v = strtoull(e, &end, 10);
+    if (end == e || *end != 0 || v == 0 || (v & (v - 1)) != 0 || v > SR_TILE || v < 2ull * top_n) {
+      set_err(c, "grim_search_create: GRIM_SEARCH_TILE must be a power of two with 2 top_n <= tile <= " + std::to_string(SR_TILE));
+      return nullptr;
+    }
+    tile = (uint32_t)v;
+  }
+  grim_match *m = grim_match_create(c, keep_mask, n_alleles);
+  if (!m) return nullptr;
+  use_device(c->device);
+  grim_search *s = new grim_search();
+  s->ctx = c;
+  s->m = m;
+  s->top_n = top_n;
+  s->tile = tile;
+  s->min_p0 = min_p0;
+  bool ok = hipMalloc((void **)&s->d_cand, 8) == hipSuccess;
+  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&s->ev[k]) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    set_err(c, "grim_search_create: device allocation failed");
+    grim_search_free(s);
+    return nullptr;
+  }
+  return s;
+}
+
+extern "C" void grim_search_free(grim_search *s) {
+  if (!s) return;
+  use_device(s->ctx->device);
+  hipStreamSynchronize(s->ctx->stream);
+  void *dev[] = {s->d_ids, s->d_keys[0], s->d_keys[1], s->d_cnt[0], s->d_cnt[1], s->d_hits[0], s->d_hits[1], s->d_run_keys[0],
+                 s->d_run_keys[1], s->d_run_cnt[0], s->d_run_cnt[1], s->d_cand};
+  for (void *p : dev)
+    if (p) hipFree(p);
+  for (int k = 0; k < 2; ++k)
+    if (s->ev[k]) hipEventDestroy(s->ev[k]);
+  grim_match_free(s->m);
+  delete s;
+}
+
+extern "C" int grim_search_set_patients(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
+  if (!s) return -1;
+  sr_empty(s);
+  return grim_match_set_patients(s->m, res, n, rows, n_rows);
+}
+
+extern "C" int grim_search_reset(grim_search *s) {
+  if (!s) return -1;
+  sr_empty(s);
+  return 0;
+}
+
+// the selection of one run: the matcher holds the records of n donors; ids on the host.  The running list changes hands only
+// when everything has worked.
+static int sr_select(grim_search *s, const char *who, const uint32_t *ids, uint32_t n) {
+  grim_ctx *c = s->ctx;
+  grim_match *m = s->m;
+  hipStream_t st = c->stream;
+  const uint32_t n_p = m->P.n, top_n = s->top_n, tile = s->tile, per = tile / top_n;
+  if (n == 0 || n_p == 0) return 0;
+  const uint32_t tiles0 = (n + tile - 1) / tile;
+  const uint64_t lists0 = (uint64_t)n_p * (tiles0 + 1ull);  // every level writes fewer lists than level 0
+  bool ok = true;
+  if ((uint64_t)n + 1 > s->ids_cap) {
+    s->ids_cap = 0;
+    if ((ok = em_grow(s->d_ids, (uint64_t)n + 1))) s->ids_cap = (uint64_t)n + 1;
+  }
+  if (ok && lists0 > s->cnt_cap) {
+    s->cnt_cap = s->keys_cap = 0;
+    ok = em_grow(s->d_cnt[0], lists0) && em_grow(s->d_cnt[1], lists0) && em_grow(s->d_keys[0], lists0 * top_n) &&
+         em_grow(s->d_keys[1], lists0 * top_n);
+    if (ok) s->cnt_cap = lists0, s->keys_cap = lists0 * top_n;
+  }
+  if (ok && (uint64_t)n_p > s->run_cap) {
+    if (s->have_running) {  // cannot be: the patients have not changed since the lists were made
+      set_err(c, std::string(who) + ": the running lists are smaller than the patients (internal)");
+      return -1;
+    }
+    s->run_cap = 0;
+    for (int k = 0; ok && k < 2; ++k)
+      ok = em_grow(s->d_hits[k], (uint64_t)n_p * top_n) && em_grow(s->d_run_keys[k], (uint64_t)n_p * top_n) && em_grow(s->d_run_cnt[k], (uint64_t)n_p);
+    if (ok) s->run_cap = n_p;
+  }
+  if (!ok) {
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
+  }
+  HIPCHK(hipMemcpyAsync(s->d_ids, ids, 4ull * n, hipMemcpyHostToDevice, st), c, -1);
+  HIPCHK(hipMemsetAsync(s->d_cand, 0, 8, st), c, -1);
+  HIPCHK(hipEventRecord(s->ev[0], st), c, -1);
+  const int cur = s->cur, nxt = cur ^ 1;
+  const SrKey *extra = s->have_running ? s->d_run_keys[cur] : nullptr;
+  const uint32_t *extra_cnt = s->have_running ? s->d_run_cnt[cur] : nullptr;
+  int side = 0;  // d_keys[side] holds the lists of the level just written
+  for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {  // the grid's second dimension ends at 65535
+    const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+    hipLaunchKernelGGL(sr_tile_kernel, dim3(tiles0, np), dim3(SR_THREADS), 0, st, m->d_out, s->d_ids, m->P.flags, m->D.flags, n_p, p0, n,
+                       s->min_p0, (const SrKey *)nullptr, (const uint32_t *)nullptr, 0u, (const SrKey *)nullptr,
+                       (const uint32_t *)nullptr, tile, top_n, s->d_keys[0], s->d_cnt[0], s->d_cand);
+  }
+  uint32_t lists = tiles0;
+  while (lists + (extra ? 1u : 0u) > 1u) {  // merging levels: per >= 2 lists become one
+    const uint32_t out_lists = (lists + (extra ? 1u : 0u) + per - 1) / per;
+    for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {
+      const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+      hipLaunchKernelGGL(sr_tile_kernel, dim3(out_lists, np), dim3(SR_THREADS), 0, st, (const double *)nullptr, (const uint32_t *)nullptr,
+                         (const uint8_t *)nullptr, (const uint8_t *)nullptr, n_p, p0, 0u, s->min_p0, s->d_keys[side], s->d_cnt[side], lists,
+                         extra, extra_cnt, tile, top_n, s->d_keys[side ^ 1], s->d_cnt[side ^ 1], s->d_cand);
+    }
+    side ^= 1;
+    lists = out_lists;
+    extra = nullptr;
+    extra_cnt = nullptr;
+  }
+  for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {
+    const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+    hipLaunchKernelGGL(sr_gather_kernel, dim3(np), dim3(64), 0, st, s->d_keys[side], s->d_cnt[side], lists, m->d_out, n_p, p0, n,
+                       s->have_running ? s->d_hits[cur] : (const SrHit *)nullptr, top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt]);
+  }
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(s->ev[1], st), c, -1);
+  unsigned long long cand = 0;
+  HIPCHK(hipMemcpyAsync(&cand, s->d_cand, 8, hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]), c, -1);
+  s->cur = nxt;
+  s->have_running = true;
+  for (int k = 0; k < 7; ++k) s->sum[k] += m->stat[k];
+  s->sum[7] += cand;
+  s->select_ms = ms;
+  s->kernel_ms = m->last_ms + ms;
+  return 0;
+}
+
+extern "C" int grim_search_run(grim_search *s, grim_batch *b, const uint32_t *donor_ids) {
+  if (!s || !b) return -1;
+  s->select_ms = s->kernel_ms = 0.0;
+  if (b->n_subj && !donor_ids) {
+    set_err(s->ctx, "grim_search_run: donor_ids is null");
+    return -3;
+  }
+  const int rc = grim_match_run(s->m, b);
+  if (rc != 0) return rc;
+  return sr_select(s, "grim_search_run", donor_ids, s->m->n_donors);
+}
+
+extern "C" int grim_search_run_records(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows,
+                                       const uint32_t *donor_ids) {
+  if (!s) return -1;
+  s->select_ms = s->kernel_ms = 0.0;
+  if (n && !donor_ids) {
+    set_err(s->ctx, "grim_search_run_records: donor_ids is null");
+    return -3;
+  }
+  const int rc = grim_match_run_records(s->m, res, n, rows, n_rows);
+  if (rc != 0) return rc;
+  return sr_select(s, "grim_search_run_records", donor_ids, s->m->n_donors);
+}
+
+extern "C" int grim_search_results(grim_search *s, grim_search_hit *hits, uint32_t *n_hits) {
+  if (!s) return -1;
+  grim_ctx *c = s->ctx;
+  use_device(c->device);
+  const uint32_t n_p = s->m->P.n;
+  const uint64_t slots = (uint64_t)n_p * s->top_n;
+  if (!s->have_running) {  // empty lists
+    if (hits)
+      for (uint64_t k = 0; k < slots; ++k) {
+        memset(&hits[k], 0, sizeof(grim_search_hit));
+        hits[k].donor = GRIM_SEARCH_NO_DONOR;
+      }
+    if (n_hits)
+      for (uint32_t p = 0; p < n_p; ++p) n_hits[p] = 0;
+    return 0;
+  }
+  if (hits && slots) HIPCHK(hipMemcpy(hits, s->d_hits[s->cur], sizeof(grim_search_hit) * slots, hipMemcpyDeviceToHost), c, -1);
+  if (n_hits && n_p) HIPCHK(hipMemcpy(n_hits, s->d_run_cnt[s->cur], 4ull * n_p, hipMemcpyDeviceToHost), c, -1);
+  return 0;
+}
+
+extern "C" int grim_search_flags(grim_search *s, uint8_t *patient_flags, uint8_t *donor_flags) {
+  if (!s) return -1;
+  return grim_match_results(s->m, nullptr, patient_flags, donor_flags);
+}
+
+extern "C" uint32_t grim_search_patients(const grim_search *s) { return s ? s->m->P.n : 0; }
+extern "C" uint32_t grim_search_donors(const grim_search *s) { return s ? s->m->n_donors : 0; }
+extern "C" uint32_t grim_search_top_n(const grim_search *s) { return s ? s->top_n : 0; }
+extern "C" double grim_search_kernel_ms(const grim_search *s) { return s ? s->kernel_ms : 0.0; }
+extern "C" double grim_search_select_ms(const grim_search *s) { return s ? s->select_ms : 0.0; }
+
+extern "C" int grim_search_stats(const grim_search *s, uint64_t out[8]) {
+  if (!s || !out) return -1;
+  for (int k = 0; k < 8; ++k) out[k] = s->sum[k];
   return 0;
 }

@@ -627,6 +627,156 @@ class Matcher:
             pass
 
 
+# ---- donor search (grim_search_*): each patient's best top_n donors over any number of runs, selected on the device ----
+EXPORTS += [
+    "grim_search_create", "grim_search_set_patients", "grim_search_reset", "grim_search_run", "grim_search_run_records",
+    "grim_search_results", "grim_search_flags", "grim_search_patients", "grim_search_donors", "grim_search_top_n",
+    "grim_search_stats", "grim_search_kernel_ms", "grim_search_select_ms", "grim_search_free",
+]
+
+SEARCH_DT = np.dtype([("donor", "<u4"), ("reserved", "<u4"), ("rec", MATCH_DT)])
+assert SEARCH_DT.itemsize == 136
+SEARCH_MAX_N = 256
+SEARCH_TILE = 2048  # entries a workgroup sorts at a time (GRIM_SEARCH_TILE lowers it, for tests)
+SEARCH_NO_DONOR = 0xFFFFFFFF
+SEARCH_STATS = MATCH_STATS + ("candidates",)
+
+_search_ready = False
+
+
+def _search_lib():
+    global _search_ready
+    L = lib()
+    if not _search_ready:
+        L.grim_search_create.restype = C.c_void_p
+        L.grim_search_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_double]
+        L.grim_search_set_patients.restype = C.c_int
+        L.grim_search_set_patients.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.grim_search_reset.restype = C.c_int
+        L.grim_search_reset.argtypes = [C.c_void_p]
+        L.grim_search_run.restype = C.c_int
+        L.grim_search_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_search_run_records.restype = C.c_int
+        L.grim_search_run_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.grim_search_results.restype = C.c_int
+        L.grim_search_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_search_flags.restype = C.c_int
+        L.grim_search_flags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for name in ("grim_search_patients", "grim_search_donors", "grim_search_top_n"):
+            getattr(L, name).restype = C.c_uint32
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.grim_search_stats.restype = C.c_int
+        L.grim_search_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        for name in ("grim_search_kernel_ms", "grim_search_select_ms"):
+            getattr(L, name).restype = C.c_double
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.grim_search_free.argtypes = [C.c_void_p]
+        _search_ready = True
+    return L
+
+
+class Searcher:
+    """grim_search: every patient's first top_n donors by match probability (mm[0] down, then mm[1] down, then id up) among the
+    pairs with mm[0] >= min_p0, over all runs since the patients were set or the search was reset, selected on the device
+    (include/grim_hip.h, the grim_search_* block).  results() and stats() speak of all runs so far; flags(), donors(),
+    kernel_ms() and select_ms() of the last one."""
+
+    def __init__(self, ctx, keep_mask, n_alleles, top_n, min_p0=0.0):
+        L = _search_lib()
+        self.ctx = ctx
+        self.h = None
+        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
+        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        top_n = int(top_n)
+        if not 0 <= top_n < 1 << 32:
+            raise ValueError("top_n out of range")
+        self.h = L.grim_search_create(ctx.h, int(keep_mask), arr, top_n, float(min_p0))
+        if not self.h:
+            raise NativeError("grim_search_create failed: " + ctx.error())
+
+    @staticmethod
+    def _ids(ids, n):
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        if ids.shape != (n,):
+            raise ValueError("%d donors but ids of shape %r" % (n, ids.shape))
+        return ids
+
+    def set_patients(self, res, rows):
+        """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows; empties the hit lists"""
+        res, rows, args = Matcher._records(res, rows)
+        rc = _search_lib().grim_search_set_patients(self.h, *args)
+        if rc != 0:
+            raise NativeError("grim_search_set_patients failed (%d): %s" % (rc, self.ctx.error()))
+
+    def reset(self):
+        """empties the hit lists and the summed statistics; the patients stay"""
+        if _search_lib().grim_search_reset(self.h) != 0:
+            raise NativeError("grim_search_reset failed: " + self.ctx.error())
+
+    def run(self, batch, ids):
+        """one DeviceBatch after its run() as donors, where its rows lie; ids: one uint32 per subject of the batch"""
+        ids = self._ids(ids, batch.n)
+        rc = _search_lib().grim_search_run(self.h, batch.h, _ptr(ids) if ids.size else None)
+        if rc != 0:
+            raise NativeError("grim_search_run failed (%d): %s" % (rc, self.ctx.error()))
+
+    def run_records(self, res, rows, ids):
+        """host records as donors, through the same kernels"""
+        res, rows, args = Matcher._records(res, rows)
+        ids = self._ids(ids, res.shape[0])
+        rc = _search_lib().grim_search_run_records(self.h, *args, _ptr(ids) if ids.size else None)
+        if rc != 0:
+            raise NativeError("grim_search_run_records failed (%d): %s" % (rc, self.ctx.error()))
+
+    def patients(self):
+        return int(_search_lib().grim_search_patients(self.h))
+
+    def donors(self):
+        return int(_search_lib().grim_search_donors(self.h))
+
+    def top_n(self):
+        return int(_search_lib().grim_search_top_n(self.h))
+
+    def results(self):
+        """-> (hits SEARCH_DT[patients][top_n], n_hits u32[patients])"""
+        n_p, top_n = self.patients(), self.top_n()
+        hits = np.zeros((n_p, top_n), dtype=SEARCH_DT)
+        n_hits = np.zeros(n_p, dtype=np.uint32)
+        if _search_lib().grim_search_results(self.h, _ptr(hits) if hits.size else None, _ptr(n_hits) if n_p else None) != 0:
+            raise NativeError("grim_search_results failed: " + self.ctx.error())
+        return hits, n_hits
+
+    def flags(self):
+        """-> (patient flags u8[patients], donor flags u8[donors of the last run])"""
+        n_p, n_d = self.patients(), self.donors()
+        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
+        if _search_lib().grim_search_flags(self.h, _ptr(pf) if n_p else None, _ptr(df) if n_d else None) != 0:
+            raise NativeError("grim_search_flags failed: " + self.ctx.error())
+        return pf, df
+
+    def stats(self):
+        out = (C.c_uint64 * 8)()
+        _search_lib().grim_search_stats(self.h, out)
+        return {k: int(v) for k, v in zip(SEARCH_STATS, out)}
+
+    def kernel_ms(self):
+        return float(_search_lib().grim_search_kernel_ms(self.h))
+
+    def select_ms(self):
+        return float(_search_lib().grim_search_select_ms(self.h))
+
+    def close(self):
+        if self.h:
+            _search_lib().grim_search_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ======================================================================================================
 # host-side helpers of the library (C++: allele dictionary, tokenizer, formatter) -- no GPU needed
 # ======================================================================================================

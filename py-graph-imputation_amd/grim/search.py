@@ -1,0 +1,258 @@
+"""
+Donor search: each patient's best N donors out of a registry, ranked by the probability of a full match.
+
+The records are those of `grim.match`, bit for bit; what is new is the selection and its order:
+
+    a pair (patient, donor) is a candidate iff its record is computed and mm[0] >= min_p0;
+    candidate x comes before candidate y iff  x.mm[0] > y.mm[0],
+                                          or  the mm[0] are equal and x.mm[1] > y.mm[1],
+                                          or  both are equal and x.id < y.id        (as a Python key: (-mm0, -mm1, id));
+    per patient: the first top_n candidates in that order over all donors, n_hits of them, in top_n slots of nat.SEARCH_DT
+    (donor id, 0, record); the unused slots are donor = 0xFFFFFFFF with a zero record.
+
+Every mm value of a computed pair is finite and >= +0.0 and the ids are distinct, so the order is strict and the answer does
+not depend on how the donors are cut into runs or in which order the runs come.
+
+`search_donors` runs it on the device (csrc/grim_search.h): the donors are streamed block by block, the selection stays in
+HBM, and patients x top_n hits come down once, after the last block.  `search_records` is the same selection over record
+arrays in plain Python, laid out as the device lays it out; `search_umug_text` the same over `.umug` text.  The three agree
+bit for bit.  There is no CPU fallback of the device functions.
+"""
+
+import math
+import os
+
+import numpy as np
+
+from . import _native as nat
+from .match import _Block, _Folder, _keep_mask, _slots_of, _store, line_id, match_records, match_umug_text
+
+
+def _check(top_n, min_p0):
+    top_n, min_p0 = int(top_n), float(min_p0)
+    if not 1 <= top_n <= nat.SEARCH_MAX_N:
+        raise ValueError("top_n must be 1..%d" % nat.SEARCH_MAX_N)
+    if math.isnan(min_p0):
+        raise ValueError("min_p0 is not a number")
+    return top_n, min_p0
+
+
+def _empty_hits(n, top_n):
+    hits = np.zeros((n, top_n), dtype=nat.SEARCH_DT)
+    hits["donor"] = nat.SEARCH_NO_DONOR
+    return hits
+
+
+def search_records(pres, prows, donor_runs, keep_mask, n_alleles, top_n, min_p0):
+    """The selection on record arrays as grim_search_run_records defines it (include/grim_hip.h).  `donor_runs`: a list of
+    (res, rows, ids), nat.RESULT_DT / nat.ROW_DT arrays and one id per donor, distinct over all runs.  Runs `match_records`
+    per run, keeps the computed pairs with mm[0] >= min_p0 and sorts them -> (hits nat.SEARCH_DT[P][top_n], n_hits u32[P],
+    stats), laid out as the device lays them out: stats are each run's match statistics summed, and `candidates`."""
+    top_n, min_p0 = _check(top_n, min_p0)
+    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
+    stats = dict.fromkeys(nat.SEARCH_STATS, 0)
+    found = [[] for _ in range(len(pres))]  # per patient: (-mm0, -mm1, id, record)
+    for res, rows, ids in donor_runs:
+        if len(ids) != len(res):
+            raise ValueError("%d donors but %d ids" % (len(res), len(ids)))
+        rec, pf, df, run = match_records(pres, prows, res, rows, keep_mask, n_alleles)
+        for k in nat.MATCH_STATS:
+            stats[k] += run[k]
+        for p in np.flatnonzero((pf & ready) == nat.MATCH_VALID):
+            for d in np.flatnonzero((df & ready) == nat.MATCH_VALID):
+                mm0 = float(rec[p, d]["mm"][0])
+                if mm0 >= min_p0:
+                    found[p].append((-mm0, -float(rec[p, d]["mm"][1]), int(ids[d]), rec[p, d]))
+                    stats["candidates"] += 1
+    hits = _empty_hits(len(pres), top_n)
+    n_hits = np.zeros(len(pres), dtype=np.uint32)
+    for p, cands in enumerate(found):
+        cands.sort(key=lambda c: c[:3])
+        n_hits[p] = min(top_n, len(cands))
+        for k, (_, _, donor, rec) in enumerate(cands[:top_n]):
+            hits[p, k]["donor"] = donor
+            hits[p, k]["rec"] = rec
+    return hits, n_hits, stats
+
+
+def search_umug_text(patient_text, donor_text, keep_loci, top_n, min_p0=0.0):
+    """The selection on `.umug` text through `match_umug_text`; a donor's id is its position in the donor text -> (patient ids,
+    donor ids, hits): hits[p] is the list of (donor position, mm[0..2|K|], {locus name: probability of no mismatch}) of the
+    patient's first top_n donors with mm[0] >= min_p0, in order."""
+    top_n, min_p0 = _check(top_n, min_p0)
+    pid, did, records = match_umug_text(patient_text, donor_text, keep_loci)
+    hits = []
+    for line in records:
+        cands = [(-H[0], -H[1], d) for d, (H, _) in enumerate(line) if H[0] >= min_p0]
+        cands.sort()
+        hits.append([(d,) + line[d] for _, _, d in cands[:top_n]])
+    return pid, did, hits
+
+
+def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_loci, top_n, min_p0=0.0, block_lines=65536, planb=None,
+                  em=False):
+    """Every patient's first `top_n` donors on the device.  Arguments as `match_probabilities`: `patient_lines`: input lines;
+    `donor_lines_or_path`: input lines (a list) or the path of an input file; `config`: the configuration dict of
+    `load_config`; `keep_loci`: locus names of its loci_map.  The patients are imputed as one device batch and set once; the
+    donors are cut into blocks of `block_lines` lines exactly as `match_probabilities` cuts them, each tokenised, imputed as
+    one device batch and matched where its rows lie, and the selection of every block is merged on the device with what the
+    earlier blocks left; a donor's id is its line number in the donor input.  The hits are fetched once, after the last block.
+    Pairs the device leaves out because a subject holds an allele the dictionary does not know are folded here on allele
+    text, thresholded, kept in a per-patient list trimmed to `top_n` and merged with the device's hits at the end under the
+    same order (the first N of a union are among the first N of each part, so the merge is exact).  A patient with such an
+    allele at a kept locus is therefore searched entirely on the host: slow, and correct.
+    -> (patient_ok, hits, n_hits, stats): hits is nat.SEARCH_DT[len(patient_lines)][top_n], hits["donor"] donor line numbers,
+    n_hits u32[len(patient_lines)]; patient_ok says which lines have genotype rows (the others have no hits); stats are the
+    match statistics as `match_probabilities` sums them, `candidates` (device and host), and `blocks`, `kernel_ms`,
+    `select_ms`, `host_pairs` (pairs folded on text) and `download_bytes` (hits and counts fetched from the device).  The cuts
+    do not show in any byte.  Subjects the device cannot answer follow `imputation.on_unsupported` as in
+    `impute_lines_block`."""
+    from .imputation.impute import UnsupportedSubjects
+
+    top_n, min_p0 = _check(top_n, min_p0)
+    g = imputation.netGraph
+    mask = _keep_mask(g.locus_slot, keep_loci)
+    slots = _slots_of(mask)
+    if isinstance(donor_lines_or_path, (str, bytes, os.PathLike)):
+        with open(donor_lines_or_path) as fh:
+            dlines = fh.read().splitlines()
+    else:
+        dlines = [l.rstrip("\n") for l in donor_lines_or_path]
+    plines = [l.rstrip("\n") for l in patient_lines]
+    if len(plines) > nat.MATCH_MAX_PAIRS:
+        raise ValueError("%d patients: more than %d pairs with a single donor" % (len(plines), nat.MATCH_MAX_PAIRS))
+    if len(dlines) >= nat.SEARCH_NO_DONOR:
+        raise ValueError("%d donor lines: a line number must fit a hit's donor field" % len(dlines))
+    if planb is None:
+        planb = config["planb"]
+    block_lines = max(1, min(int(block_lines), nat.MATCH_MAX_PAIRS // max(1, len(plines))))
+    cfg = dict(config, output_MUUG=True)
+    params = imputation._params(cfg, planb, False, em)
+    ps, _ = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
+    ctx = nat.default_context(imputation.device)
+    dgraph = g.device(ctx)
+    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))] + [0] * (nat.MAXL - len(g.full_loci))
+    searcher = nat.Searcher(ctx, mask, n_alleles, top_n, min_p0)
+    imputation.unsupported = []
+    stats = dict.fromkeys(nat.SEARCH_STATS, 0)
+    stats.update(blocks=0, kernel_ms=0.0, select_ms=0.0, host_pairs=0, download_bytes=0)
+    hits = _empty_hits(len(plines), top_n)
+    n_hits = np.zeros(len(plines), dtype=np.uint32)
+    patient_ok = np.zeros(len(plines), dtype=bool)
+    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
+    folder = _Folder(len(slots))  # of the text route
+    pblock = None
+
+    def check(block, flags):
+        bad = block.bad + (block.unsupported() if block.batch is not None and not flags.all() else [])
+        imputation.unsupported += sorted(bad)
+        if imputation.unsupported and imputation.on_unsupported == "raise":
+            raise UnsupportedSubjects(imputation.unsupported)
+        if np.count_nonzero(flags & nat.MATCH_UNDEFINED):
+            raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their match is "
+                             "not defined" % np.count_nonzero(flags & nat.MATCH_UNDEFINED))
+
+    try:
+        pblock = _Block(imputation, ctx, dgraph, params, ps, plines, 0, planb)
+        pf = np.zeros(0, dtype=np.uint8)
+        if pblock.batch is not None:
+            searcher.set_patients(*pblock.records())
+            pf = searcher.flags()[0]
+            pblock.batch.close()  # the records are on the host, the patients prepared on the device
+        check(pblock, pf)
+        patient_ok[pblock.line_of[np.flatnonzero(pf & nat.MATCH_VALID)]] = True
+        stats["patients_valid"] = int(np.count_nonzero(pf & nat.MATCH_VALID))
+        stats["patients_private"] = int(np.count_nonzero(pf & nat.MATCH_PRIVATE))
+        ptext = {}  # patient -> its rows on allele text
+        host = {}   # patient -> [((-mm0, -mm1, id), H, L)] of the pairs folded here, at most top_n after a block
+        for lo in range(0, len(dlines), block_lines):
+            block = _Block(imputation, ctx, dgraph, params, ps, dlines[lo:lo + block_lines], lo, planb)
+            try:
+                if block.batch is None or not len(pf):
+                    check(block, np.zeros(0, dtype=np.uint8))
+                    continue
+                ids = lo + block.line_of
+                searcher.run(block.batch, ids.astype(np.uint32))
+                df = searcher.flags()[1]
+                check(block, df)
+                stats["donors_valid"] += int(np.count_nonzero(df & nat.MATCH_VALID))
+                stats["donors_private"] += int(np.count_nonzero(df & nat.MATCH_PRIVATE))
+                stats["kernel_ms"] += searcher.kernel_ms()
+                stats["select_ms"] += searcher.select_ms()
+                stats["blocks"] += 1
+                # pairs the device left out for a private allele: the same fold on allele text
+                dtext = {}
+                for p in np.flatnonzero(pf & nat.MATCH_VALID):
+                    for d in np.flatnonzero(df & nat.MATCH_VALID):
+                        if (pf[p] & ready) == nat.MATCH_VALID and (df[d] & ready) == nat.MATCH_VALID:
+                            continue
+                        if p not in ptext:
+                            ptext[p] = pblock.text_subject(g, int(p), slots, n_alleles, folder)
+                        if d not in dtext:
+                            dtext[d] = block.text_subject(g, int(d), slots, n_alleles, folder)
+                        H, L = folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
+                        stats["host_pairs"] += 1
+                        if H[0] >= min_p0:
+                            host.setdefault(int(p), []).append(((-H[0], -H[1], int(ids[d])), H, L))
+                            stats["candidates"] += 1
+                for p in host:
+                    host[p].sort(key=lambda c: c[0])
+                    del host[p][top_n:]
+            finally:
+                block.close()
+        if len(pf):
+            dev_hits, dev_n = searcher.results()  # once, after the last block
+            stats["download_bytes"] = dev_hits.nbytes + dev_n.nbytes
+            total = searcher.stats()
+            stats["pairs"], stats["row_pairs"] = total["pairs"], total["row_pairs"]
+            stats["candidates"] += total["candidates"]
+            for p in range(len(pf)):
+                line = int(pblock.line_of[p])
+                if p not in host:
+                    hits[line], n_hits[line] = dev_hits[p], dev_n[p]
+                    continue
+                merged = [((-float(h["rec"]["mm"][0]), -float(h["rec"]["mm"][1]), int(h["donor"])), h) for h in dev_hits[p, :int(dev_n[p])]]
+                merged += [(key, (H, L)) for key, H, L in host[p]]
+                merged.sort(key=lambda c: c[0])
+                n_hits[line] = min(top_n, len(merged))
+                for k, (key, what) in enumerate(merged[:top_n]):
+                    hits[line, k]["donor"] = key[2]
+                    if isinstance(what, tuple):
+                        _store(hits[line, k]["rec"], slots, *what)
+                    else:
+                        hits[line, k]["rec"] = what["rec"]
+    finally:
+        if pblock is not None:
+            pblock.close()
+        searcher.close()
+    return patient_ok, hits, n_hits, stats
+
+
+def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, graph=None, block_lines=65536):
+    """The configuration's input file as donors against the input file `patients_path`, on `graph` (built from the
+    configuration's graph CSVs when None) -> a CSV at `out_path`: a header `patient_id,rank,donor_id,mm0,...,mm{2|K|},<kept
+    locus names>`, then per patient its hits in order, ranks from 0, patient-major, floats written with repr.  Paths are
+    taken as the configuration gives them.  -> stats"""
+    from .grim import graph_instance
+    from .imputation.impute import Imputation
+    from .run_impute_def import load_config
+
+    config, _ = load_config(conf_file)
+    if graph is None:
+        graph = graph_instance(config)
+    imp = Imputation(graph, config)
+    with open(patients_path) as fh:
+        plines = fh.read().splitlines()
+    with open(config["imputation_input_file"]) as fh:
+        dlines = fh.read().splitlines()
+    pok, hits, n_hits, stats = search_donors(imp, plines, dlines, config, keep_loci, top_n, min_p0=min_p0, block_lines=block_lines)
+    slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
+    nb = 2 * len(slots) + 1
+    with open(out_path, "w") as fh:
+        fh.write(",".join(["patient_id", "rank", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots]) + "\n")
+        for p in np.flatnonzero(pok):
+            for k in range(int(n_hits[p])):
+                r = hits[p, k]["rec"]
+                vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
+                fh.write("%s,%d,%s,%s\n" % (line_id(plines[p]), k, line_id(dlines[int(hits[p, k]["donor"])]), ",".join(repr(v) for v in vals)))
+    return stats
