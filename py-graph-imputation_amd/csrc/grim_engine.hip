@@ -1747,6 +1747,127 @@ static void batch_destroy(grim_batch *b) {
 }
 
 // =================================================================================================
+// Shared pieces of the finished-batch consumers below (M-step, marginal tables, match probabilities, donor search): each
+// consumer is a plain struct that holds these by value
+// =================================================================================================
+// A device array kept across calls and grown on demand.  Growing discards the contents; a failed grow leaves it empty
+// (null, capacity 0), so that the next call tries again.  Kernels are handed these pointers even for a side without rows:
+// a caller that must never pass null asks for one element more than it needs.
+template <typename T>
+struct DevBuf {
+  T *p = nullptr;
+  uint64_t cap = 0;  // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  // room for `need` elements; a grow allocates need + headroom
+  bool reserve(uint64_t need, uint64_t headroom = 0) {
+    if (need <= cap) return true;
+    release();
+    if (hipMalloc((void **)&p, sizeof(T) * (need + headroom)) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      return false;
+    }
+    cap = need + headroom;
+    return true;
+  }
+  operator T *() const { return p; }
+};
+
+// several buffers to one size; false if any of them fails
+template <typename... B>
+static bool reserve_all(uint64_t need, uint64_t headroom, B &...bufs) {
+  return (bufs.reserve(need, headroom) && ...);
+}
+
+template <int N>
+struct Events {
+  hipEvent_t ev[N] = {};
+  Events() = default;
+  Events(const Events &) = delete;
+  Events &operator=(const Events &) = delete;
+  ~Events() {
+    for (hipEvent_t e : ev)
+      if (e) hipEventDestroy(e);
+  }
+  bool create() {
+    for (hipEvent_t &e : ev)
+      if (hipEventCreate(&e) != hipSuccess) return false;
+    return true;
+  }
+  hipEvent_t operator[](int k) const { return ev[k]; }
+};
+
+static bool refuse(grim_ctx *c, const char *who, const char *why) {
+  set_err(c, std::string(who) + ": " + why);
+  return false;
+}
+
+// The door of a consumer that works on a finished batch where its rows lie.  n_pops == 0: the consumer needs genotype rows
+// and keeps the locus slots of keep_mask; n_pops > 0: it needs phased rows that carry populations, n_pops of them.  The
+// first check that fails sets the message; the caller returns -3.
+static bool batch_door(grim_ctx *c, const char *who, const grim_batch *b, uint32_t keep_mask, uint32_t n_pops) {
+  if (b->ctx != c) return refuse(c, who, "the batch belongs to another context");
+  if (n_pops && (!b->a.prm.em_mr || !b->a.prm.out_haps))
+    return refuse(c, who, "the batch was built without em_mr / out_haps: its phased rows carry no populations");
+  if (!b->ran_ok) return refuse(c, who, "the batch holds no finished run (call grim_batch_run first)");
+  if (n_pops) return b->g->d.P == n_pops || refuse(c, who, "the batch's graph has another number of populations");
+  if (!b->a.prm.out_muug) return refuse(c, who, "the batch was built with out_muug off: it holds no genotype rows");
+  if (keep_mask == 0 || b->g->d.n_loci > GRIM_MAXL || (keep_mask >> b->g->d.n_loci) != 0)
+    return refuse(c, who, "keep_mask is empty or names a locus slot the graph does not have");
+  return true;
+}
+
+// the door of a consumer that is given host records; the caller returns -3
+static bool records_door(grim_ctx *c, const char *who, uint32_t keep_mask, const grim_subject_result *res, uint32_t n, const grim_row *rows,
+                         uint64_t n_rows) {
+  if (keep_mask == 0 || (keep_mask >> GRIM_MAXL) != 0) return refuse(c, who, "keep_mask is empty or names a locus slot beyond GRIM_MAXL");
+  if ((n && !res) || (n_rows && !rows) || n_rows > 0x7FFFFFFFull) return refuse(c, who, "bad arguments");
+  return true;
+}
+
+// host records on the device, kept and grown
+struct RecordsUpload {
+  DevBuf<grim_subject_result> res;
+  DevBuf<grim_row> rows;
+  // res[n], rows[n_rows] of the host into the buffers; the caller's arrays are free again on return
+  int upload(grim_ctx *c, const char *who, const grim_subject_result *h_res, uint32_t n, const grim_row *h_rows, uint32_t n_rows) {
+    if (!res.reserve((uint64_t)n + 1) || !rows.reserve((uint64_t)n_rows + 1)) {  // never an empty allocation
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    if (n) HIPCHK(hipMemcpyAsync(res, h_res, sizeof(grim_subject_result) * (uint64_t)n, hipMemcpyHostToDevice, c->stream), c, -1);
+    if (n_rows) HIPCHK(hipMemcpyAsync(rows, h_rows, sizeof(grim_row) * (uint64_t)n_rows, hipMemcpyHostToDevice, c->stream), c, -1);
+    HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+    return 0;
+  }
+};
+
+// a statistics block of the device (SLICES copies of COUNT words), slices added up; ends in a stream synchronise
+template <uint32_t COUNT, uint32_t SLICES>
+static int read_stat(grim_ctx *c, const unsigned long long *d_stat, uint64_t h[COUNT]) {
+  unsigned long long hs[COUNT * SLICES];
+  HIPCHK(hipMemcpyAsync(hs, d_stat, sizeof(hs), hipMemcpyDeviceToHost, c->stream), c, -1);
+  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+  for (uint32_t k = 0; k < COUNT; ++k) h[k] = 0;
+  for (uint32_t k = 0; k < COUNT * SLICES; ++k) h[k % COUNT] += hs[k];
+  return 0;
+}
+
+// the grid's second dimension ends at 65535: launch(p0, np) for every slab [p0, p0 + np) of n_p rows
+template <typename F>
+static void for_slabs(uint32_t n_p, F launch) {
+  for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) launch(p0, n_p - p0 < 65535u ? n_p - p0 : 65535u);
+}
+
+// =================================================================================================
 // M-step accumulator (grim_em.h): haplotype / population counts from the phased rows of finished batches
 // =================================================================================================
 static_assert(sizeof(EmSpill) == sizeof(grim_em_spill_rec) && sizeof(EmSpill) == 32, "spill record layout");
@@ -1756,16 +1877,15 @@ struct grim_em {
   EmLimits lim;
   EmTable T;               // keys / popmask / counts in HBM
   uint64_t cap;            // slots (a power of two); at most half of them are ever used
-  unsigned long long *d_stat;
-  // per-batch buffers, kept and grown: positions per subject, (group, position) ping-pong, weights, radix counts, spill
-  uint32_t *d_first, *d_grp[2], *d_idx[2], *d_cnt;
-  double *d_w, *d_ws;
-  EmSpill *d_spill;
-  uint64_t first_cap, contrib_cap, cnt_cap;
+  DevBuf<unsigned long long> d_stat;
+  // per-batch buffers: positions per subject, (group, position) ping-pong, weights, radix counts, spill
+  DevBuf<uint32_t> d_first, d_grp[2], d_idx[2], d_cnt;
+  DevBuf<double> d_w, d_ws;
+  DevBuf<EmSpill> d_spill;
   std::vector<EmSpill> spill;  // every batch's records, in contract order
   uint64_t table_used, entries, n_used, n_planc, n_contrib, n_rehash, last_unsupported;
   uint32_t batch_no;
-  hipEvent_t ev[6];
+  Events<6> ev;
   double last_ms;
 };
 
@@ -1809,9 +1929,8 @@ extern "C" grim_em *grim_em_create(grim_ctx *c, const uint32_t n_alleles[GRIM_MA
   for (int q = 0; q < GRIM_MAXL; ++q) e->lim.n_alleles[q] = n_alleles[q];
   e->cap = cap;
   bool ok = em_table_alloc(c, e->T, cap, n_pops);
-  ok = ok && hipMalloc((void **)&e->d_stat, 8 * EM_S_COUNT) == hipSuccess && hipMemsetAsync(e->d_stat, 0, 8 * EM_S_COUNT, c->stream) == hipSuccess;
-  for (int k = 0; ok && k < 6; ++k) ok = hipEventCreate(&e->ev[k]) == hipSuccess;
-  ok = ok && hipStreamSynchronize(c->stream) == hipSuccess;
+  ok = ok && e->d_stat.reserve(EM_S_COUNT) && hipMemsetAsync(e->d_stat, 0, 8 * EM_S_COUNT, c->stream) == hipSuccess;
+  ok = ok && e->ev.create() && hipStreamSynchronize(c->stream) == hipSuccess;
   if (!ok) {
     (void)hipGetLastError();
     set_err(c, "grim_em_create: device allocation failed");
@@ -1826,24 +1945,7 @@ extern "C" void grim_em_free(grim_em *e) {
   use_device(e->ctx->device);
   hipStreamSynchronize(e->ctx->stream);
   em_table_free(e->T);
-  void *dev[] = {e->d_stat, e->d_first, e->d_grp[0], e->d_grp[1], e->d_idx[0], e->d_idx[1], e->d_cnt, e->d_w, e->d_ws, e->d_spill};
-  for (void *p : dev)
-    if (p) hipFree(p);
-  for (int k = 0; k < 6; ++k)
-    if (e->ev[k]) hipEventDestroy(e->ev[k]);
   delete e;
-}
-
-template <typename T>
-static bool em_grow(T *&ptr, uint64_t n) {
-  if (ptr) hipFree(ptr);
-  ptr = nullptr;
-  if (hipMalloc((void **)&ptr, sizeof(T) * n) != hipSuccess) {
-    (void)hipGetLastError();
-    ptr = nullptr;
-    return false;
-  }
-  return true;
 }
 
 // a table twice the size, the entries moved by a kernel with their counters; returns the kernel's milliseconds or < 0
@@ -1881,34 +1983,15 @@ extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
   grim_ctx *c = e->ctx;
   e->last_ms = 0.0;
   e->last_unsupported = 0;
-  if (b->ctx != c) {
-    set_err(c, "grim_em_accumulate: the batch belongs to another context");
-    return -3;
-  }
-  if (!b->a.prm.em_mr || !b->a.prm.out_haps) {
-    set_err(c, "grim_em_accumulate: the batch was built without em_mr / out_haps: its phased rows carry no populations");
-    return -3;
-  }
-  if (!b->ran_ok) {
-    set_err(c, "grim_em_accumulate: the batch holds no finished run (call grim_batch_run first)");
-    return -3;
-  }
-  if (b->g->d.P != e->T.P) {
-    set_err(c, "grim_em_accumulate: the batch's graph has another number of populations");
-    return -3;
-  }
+  if (!batch_door(c, "grim_em_accumulate", b, 0, e->T.P)) return -3;
   use_device(c->device);
   hipStream_t st = c->stream;
   const uint32_t n = b->n_subj;
   const uint32_t batch_no = e->batch_no++;
   if (n == 0) return 0;
-  if ((uint64_t)n + 1 > e->first_cap) {
-    if (!em_grow(e->d_first, (uint64_t)n + 1)) {
-      e->first_cap = 0;
-      set_err(c, "grim_em_accumulate: device allocation failed");
-      return -1;
-    }
-    e->first_cap = (uint64_t)n + 1;
+  if (!e->d_first.reserve((uint64_t)n + 1)) {
+    set_err(c, "grim_em_accumulate: device allocation failed");
+    return -1;
   }
   // ---- rows per subject -> positions ------------------------------------------------------------------------------
   HIPCHK(hipMemsetAsync(e->d_stat, 0, 8 * 4, st), c, -1);  // the per-call words
@@ -1936,24 +2019,11 @@ extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
       if (r < 0) return -1;
       total_ms += r;
     }
-    if (C > e->contrib_cap) {
-      const uint64_t want = (uint64_t)C + C / 4;
-      e->contrib_cap = 0;
-      if (!em_grow(e->d_grp[0], want) || !em_grow(e->d_grp[1], want) || !em_grow(e->d_idx[0], want) || !em_grow(e->d_idx[1], want) ||
-          !em_grow(e->d_w, want) || !em_grow(e->d_ws, want) || !em_grow(e->d_spill, want)) {
-        set_err(c, "grim_em_accumulate: device allocation failed");
-        return -1;
-      }
-      e->contrib_cap = want;
-    }
     const uint32_t n_chunks = (C + GRIM_EM_CHUNK - 1) / GRIM_EM_CHUNK;
-    if (256ull * n_chunks + 1 > e->cnt_cap) {
-      e->cnt_cap = 0;
-      if (!em_grow(e->d_cnt, 256ull * n_chunks + 1)) {
-        set_err(c, "grim_em_accumulate: device allocation failed");
-        return -1;
-      }
-      e->cnt_cap = 256ull * n_chunks + 1;
+    if (!reserve_all(C, C / 4, e->d_grp[0], e->d_grp[1], e->d_idx[0], e->d_idx[1], e->d_w, e->d_ws, e->d_spill) ||
+        !e->d_cnt.reserve(256ull * n_chunks + 1)) {
+      set_err(c, "grim_em_accumulate: device allocation failed");
+      return -1;
     }
     HIPCHK(hipEventRecord(e->ev[2], st), c, -1);
     hipLaunchKernelGGL(em_weight_kernel, dim3((n + 3) / 4), dim3(256), 0, st, b->a.res, b->a.rows, n, e->d_first, e->T, e->lim, batch_no,
@@ -2068,18 +2138,19 @@ extern "C" int grim_em_export(grim_em *e, uint64_t *keys, uint32_t *pops, double
 struct grim_marginal {
   grim_ctx *ctx;
   uint32_t keep_mask, max_rows;
-  unsigned long long *d_stat;
-  // kept and grown: region starts per subject; scratch, output rows and result copies; the uploaded records of
+  DevBuf<unsigned long long> d_stat;
+  // region starts per subject; scratch (MgScratch), output rows and result copies; the uploaded records of
   // grim_marginal_reduce_records
-  uint32_t *d_first;
-  MgScratch G;
-  grim_row *d_orows, *d_in_rows;
-  grim_subject_result *d_ores, *d_in_res;
-  uint64_t subj_cap, row_cap, in_subj_cap, in_row_cap;
+  DevBuf<uint32_t> d_first, g_lead;
+  DevBuf<uint64_t> g_lo, g_hi;
+  DevBuf<double> g_prob, g_sum;
+  DevBuf<grim_row> d_orows;
+  DevBuf<grim_subject_result> d_ores;
+  RecordsUpload in;
   // the last reduce
   uint32_t n_subj, n_rows;
   uint64_t stat[5];
-  hipEvent_t ev[2];
+  Events<2> ev;
   double last_ms;
 };
 
@@ -2093,9 +2164,7 @@ extern "C" grim_marginal *grim_marginal_create(grim_ctx *c, uint32_t keep_mask, 
   m->ctx = c;
   m->keep_mask = keep_mask;
   m->max_rows = max_rows;
-  bool ok = hipMalloc((void **)&m->d_stat, 8 * MG_S_COUNT * MG_S_SLICES) == hipSuccess;
-  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&m->ev[k]) == hipSuccess;
-  if (!ok) {
+  if (!m->d_stat.reserve(MG_S_COUNT * MG_S_SLICES) || !m->ev.create()) {
     (void)hipGetLastError();
     set_err(c, "grim_marginal_create: device allocation failed");
     grim_marginal_free(m);
@@ -2108,11 +2177,6 @@ extern "C" void grim_marginal_free(grim_marginal *m) {
   if (!m) return;
   use_device(m->ctx->device);
   hipStreamSynchronize(m->ctx->stream);
-  void *dev[] = {m->d_stat, m->d_first, m->G.lo, m->G.hi, m->G.prob, m->G.sum, m->G.lead, m->d_orows, m->d_in_rows, m->d_ores, m->d_in_res};
-  for (void *p : dev)
-    if (p) hipFree(p);
-  for (int k = 0; k < 2; ++k)
-    if (m->ev[k]) hipEventDestroy(m->ev[k]);
   delete m;
 }
 
@@ -2127,39 +2191,25 @@ static int mg_run(grim_marginal *m, const char *who, const grim_subject_result *
   grim_ctx *c = m->ctx;
   hipStream_t st = c->stream;
   if (n == 0) return 0;
-  if ((uint64_t)n + 1 > m->subj_cap) {
-    m->subj_cap = 0;
-    if (!em_grow(m->d_first, (uint64_t)n + 1) || !em_grow(m->d_ores, (uint64_t)n)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    m->subj_cap = (uint64_t)n + 1;
+  if (!m->d_first.reserve((uint64_t)n + 1) || !m->d_ores.reserve(n) ||
+      !reserve_all(rows_used, rows_used / 4, m->g_lo, m->g_hi, m->g_prob, m->g_sum, m->g_lead, m->d_orows)) {
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
   }
-  if (rows_used > m->row_cap) {
-    const uint64_t want = (uint64_t)rows_used + rows_used / 4;
-    m->row_cap = 0;
-    if (!em_grow(m->G.lo, want) || !em_grow(m->G.hi, want) || !em_grow(m->G.prob, want) || !em_grow(m->G.sum, want) ||
-        !em_grow(m->G.lead, want) || !em_grow(m->d_orows, want)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    m->row_cap = want;
-  }
+  const MgScratch G = {m->g_lo, m->g_hi, m->g_prob, m->g_sum, m->g_lead};
   HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MG_S_COUNT * MG_S_SLICES, st), c, -1);
   if (rows_used) HIPCHK(hipMemsetAsync(m->d_orows, 0, sizeof(grim_row) * (uint64_t)rows_used, st), c, -1);  // what a region does not use reads as zeros
   HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
   hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, m->d_first);
   hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, m->d_first, n);
   hipLaunchKernelGGL(mg_reduce_kernel, dim3(n), dim3(64), 0, st, res, rows, n, rows_used, m->d_first, rows_used, m->keep_mask, m->max_rows,
-                     m->G, m->d_ores, m->d_orows, m->d_stat);
+                     G, m->d_ores, m->d_orows, m->d_stat);
   HIPCHK(hipGetLastError(), c, -1);
   HIPCHK(hipEventRecord(m->ev[1], st), c, -1);
-  unsigned long long hs[MG_S_COUNT * MG_S_SLICES], h[MG_S_COUNT] = {0};
   uint32_t total = 0;
-  HIPCHK(hipMemcpyAsync(hs, m->d_stat, sizeof(hs), hipMemcpyDeviceToHost, st), c, -1);
+  uint64_t h[MG_S_COUNT];
   HIPCHK(hipMemcpyAsync(&total, m->d_first + n, 4, hipMemcpyDeviceToHost, st), c, -1);
-  HIPCHK(hipStreamSynchronize(st), c, -1);
-  for (uint32_t k = 0; k < MG_S_COUNT * MG_S_SLICES; ++k) h[k % MG_S_COUNT] += hs[k];
+  if (read_stat<MG_S_COUNT, MG_S_SLICES>(c, m->d_stat, h) != 0) return -1;
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]), c, -1);
   if (total > rows_used || h[MG_S_ROWS_IN] != total) {  // regions that overlap: the kernel left those that did not fit alone
@@ -2177,22 +2227,7 @@ extern "C" int grim_marginal_reduce(grim_marginal *m, grim_batch *b) {
   if (!m || !b) return -1;
   grim_ctx *c = m->ctx;
   mg_clear(m);
-  if (b->ctx != c) {
-    set_err(c, "grim_marginal_reduce: the batch belongs to another context");
-    return -3;
-  }
-  if (!b->ran_ok) {
-    set_err(c, "grim_marginal_reduce: the batch holds no finished run (call grim_batch_run first)");
-    return -3;
-  }
-  if (!b->a.prm.out_muug) {
-    set_err(c, "grim_marginal_reduce: the batch was built with out_muug off: it holds no genotype rows");
-    return -3;
-  }
-  if (m->keep_mask == 0 || b->g->d.n_loci > GRIM_MAXL || (m->keep_mask >> b->g->d.n_loci) != 0) {
-    set_err(c, "grim_marginal_reduce: keep_mask is empty or names a locus slot the graph does not have");
-    return -3;
-  }
+  if (!batch_door(c, "grim_marginal_reduce", b, m->keep_mask, 0)) return -3;
   use_device(c->device);
   return mg_run(m, "grim_marginal_reduce", b->a.res, b->a.rows, b->n_subj, b->rows_used);
 }
@@ -2202,36 +2237,11 @@ extern "C" int grim_marginal_reduce_records(grim_marginal *m, const grim_subject
   if (!m) return -1;
   grim_ctx *c = m->ctx;
   mg_clear(m);
-  if (m->keep_mask == 0 || (m->keep_mask >> GRIM_MAXL) != 0) {
-    set_err(c, "grim_marginal_reduce_records: keep_mask is empty or names a locus slot beyond GRIM_MAXL");
-    return -3;
-  }
-  if ((n_subjects && !res) || (n_rows && !rows) || n_rows > 0x7FFFFFFFull) {
-    set_err(c, "grim_marginal_reduce_records: bad arguments");
-    return -3;
-  }
+  if (!records_door(c, "grim_marginal_reduce_records", m->keep_mask, res, n_subjects, rows, n_rows)) return -3;
   use_device(c->device);
   if (n_subjects == 0) return 0;
-  if (n_subjects > m->in_subj_cap) {
-    m->in_subj_cap = 0;
-    if (!em_grow(m->d_in_res, (uint64_t)n_subjects)) {
-      set_err(c, "grim_marginal_reduce_records: device allocation failed");
-      return -1;
-    }
-    m->in_subj_cap = n_subjects;
-  }
-  if (n_rows + 1 > m->in_row_cap) {  // never an empty allocation
-    m->in_row_cap = 0;
-    if (!em_grow(m->d_in_rows, n_rows + 1)) {
-      set_err(c, "grim_marginal_reduce_records: device allocation failed");
-      return -1;
-    }
-    m->in_row_cap = n_rows + 1;
-  }
-  HIPCHK(hipMemcpyAsync(m->d_in_res, res, sizeof(grim_subject_result) * (uint64_t)n_subjects, hipMemcpyHostToDevice, c->stream), c, -1);
-  if (n_rows) HIPCHK(hipMemcpyAsync(m->d_in_rows, rows, sizeof(grim_row) * n_rows, hipMemcpyHostToDevice, c->stream), c, -1);
-  HIPCHK(hipStreamSynchronize(c->stream), c, -1);  // the caller's arrays are free again
-  return mg_run(m, "grim_marginal_reduce_records", m->d_in_res, m->d_in_rows, n_subjects, (uint32_t)n_rows);
+  if (m->in.upload(c, "grim_marginal_reduce_records", res, n_subjects, rows, (uint32_t)n_rows) != 0) return -1;
+  return mg_run(m, "grim_marginal_reduce_records", m->in.res, m->in.rows, n_subjects, (uint32_t)n_rows);
 }
 
 extern "C" uint32_t grim_marginal_subjects(const grim_marginal *m) { return m ? m->n_subj : 0; }
@@ -2256,33 +2266,31 @@ extern "C" int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]) {
 // =================================================================================================
 // Match probabilities (grim_match.h): the UMUG rows of patients against those of a finished batch of donors
 // =================================================================================================
-struct MtBuf {  // one side on the device, kept and grown
-  uint32_t *first;
-  uint64_t *a, *b;
-  double *w;
-  uint8_t *flags;
-  uint64_t subj_cap, row_cap;
+struct MtBuf {  // one side on the device
+  DevBuf<uint32_t> first;
+  DevBuf<uint64_t> a, b;
+  DevBuf<double> w;
+  DevBuf<uint8_t> flags;
   uint32_t n;  // subjects of the side
+  MtSide side() const { return {first, a, b, w, flags}; }
 };
 
 struct grim_match {
   grim_ctx *ctx;
   uint32_t keep_mask;
   EmLimits lim;
-  unsigned long long *d_stat;
+  DevBuf<unsigned long long> d_stat;
   MtBuf P, D;
-  // kept and grown: the uploaded records of grim_match_set_patients / grim_match_run_records; the result records
-  grim_row *d_in_rows;
-  grim_subject_result *d_in_res;
-  uint64_t in_subj_cap, in_row_cap;
-  double *d_out;
-  uint64_t out_cap;  // pairs
+  // the uploaded records of grim_match_set_patients and of grim_match_run_records (one pair of buffers: mt_prepare copies
+  // what a side needs out of them); the result records
+  RecordsUpload in;
+  DevBuf<double> d_out;
   bool have_patients;
   uint64_t pstat[MT_S_COUNT];  // what preparing the patients counted
   // the last run
   uint32_t n_donors;
   uint64_t stat[8];
-  hipEvent_t ev[2];
+  Events<2> ev;
   double last_ms;
 };
 
@@ -2296,9 +2304,7 @@ extern "C" grim_match *grim_match_create(grim_ctx *c, uint32_t keep_mask, const 
   m->ctx = c;
   m->keep_mask = keep_mask;
   for (int q = 0; q < GRIM_MAXL; ++q) m->lim.n_alleles[q] = n_alleles[q];
-  bool ok = hipMalloc((void **)&m->d_stat, 8 * MT_S_COUNT * MT_S_SLICES) == hipSuccess;
-  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&m->ev[k]) == hipSuccess;
-  if (!ok) {
+  if (!m->d_stat.reserve(MT_S_COUNT * MT_S_SLICES) || !m->ev.create()) {
     (void)hipGetLastError();
     set_err(c, "grim_match_create: device allocation failed");
     grim_match_free(m);
@@ -2311,12 +2317,6 @@ extern "C" void grim_match_free(grim_match *m) {
   if (!m) return;
   use_device(m->ctx->device);
   hipStreamSynchronize(m->ctx->stream);
-  void *dev[] = {m->d_stat, m->P.first, m->P.a, m->P.b, m->P.w, m->P.flags, m->D.first, m->D.a, m->D.b, m->D.w, m->D.flags,
-                 m->d_in_rows, m->d_in_res, m->d_out};
-  for (void *p : dev)
-    if (p) hipFree(p);
-  for (int k = 0; k < 2; ++k)
-    if (m->ev[k]) hipEventDestroy(m->ev[k]);
   delete m;
 }
 
@@ -2333,38 +2333,15 @@ static void mt_drop_patients(grim_match *m) {
   for (uint64_t &x : m->pstat) x = 0;
 }
 
-// the statistics block of the device, slices added up
-static int mt_read_stat(grim_match *m, uint64_t h[MT_S_COUNT]) {
-  grim_ctx *c = m->ctx;
-  unsigned long long hs[MT_S_COUNT * MT_S_SLICES];
-  HIPCHK(hipMemcpyAsync(hs, m->d_stat, sizeof(hs), hipMemcpyDeviceToHost, c->stream), c, -1);
-  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
-  for (uint32_t k = 0; k < MT_S_COUNT; ++k) h[k] = 0;
-  for (uint32_t k = 0; k < MT_S_COUNT * MT_S_SLICES; ++k) h[k % MT_S_COUNT] += hs[k];
-  return 0;
-}
-
 // count, scan, prepare: n subjects whose rows lie in [0, rows_used) of `rows` (device arrays) into side S; enqueues only
 static int mt_prepare(grim_match *m, const char *who, MtBuf &S, uint32_t side, const grim_subject_result *res, const grim_row *rows,
                       uint32_t n, uint32_t rows_used) {
   grim_ctx *c = m->ctx;
   hipStream_t st = c->stream;
-  if ((uint64_t)n + 1 > S.subj_cap) {
-    S.subj_cap = 0;
-    if (!em_grow(S.first, (uint64_t)n + 1) || !em_grow(S.flags, (uint64_t)n + 1)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    S.subj_cap = (uint64_t)n + 1;
-  }
-  if ((uint64_t)rows_used + 1 > S.row_cap) {  // never an empty allocation
-    const uint64_t want = (uint64_t)rows_used + rows_used / 4 + 1;
-    S.row_cap = 0;
-    if (!em_grow(S.a, want) || !em_grow(S.b, want) || !em_grow(S.w, want)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    S.row_cap = want;
+  if (!reserve_all((uint64_t)n + 1, 0, S.first, S.flags) ||
+      !reserve_all((uint64_t)rows_used + 1, rows_used / 4, S.a, S.b, S.w)) {  // never an empty allocation
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
   }
   hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, S.first);
   hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, S.first, n);
@@ -2374,62 +2351,24 @@ static int mt_prepare(grim_match *m, const char *who, MtBuf &S, uint32_t side, c
   return 0;
 }
 
-// res[n], rows[n_rows] of the host into the upload buffers; the caller's arrays are free again on return
-static int mt_upload(grim_match *m, const char *who, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
-  grim_ctx *c = m->ctx;
-  if ((uint64_t)n + 1 > m->in_subj_cap) {
-    m->in_subj_cap = 0;
-    if (!em_grow(m->d_in_res, (uint64_t)n + 1)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    m->in_subj_cap = (uint64_t)n + 1;
-  }
-  if ((uint64_t)n_rows + 1 > m->in_row_cap) {
-    m->in_row_cap = 0;
-    if (!em_grow(m->d_in_rows, (uint64_t)n_rows + 1)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    m->in_row_cap = (uint64_t)n_rows + 1;
-  }
-  if (n) HIPCHK(hipMemcpyAsync(m->d_in_res, res, sizeof(grim_subject_result) * (uint64_t)n, hipMemcpyHostToDevice, c->stream), c, -1);
-  if (n_rows) HIPCHK(hipMemcpyAsync(m->d_in_rows, rows, sizeof(grim_row) * (uint64_t)n_rows, hipMemcpyHostToDevice, c->stream), c, -1);
-  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
-  return 0;
-}
-
-static bool mt_records_args_ok(grim_match *m, const char *who, const grim_subject_result *res, uint32_t n, const grim_row *rows,
-                               uint32_t n_rows) {
-  if (m->keep_mask == 0 || (m->keep_mask >> GRIM_MAXL) != 0) {
-    set_err(m->ctx, std::string(who) + ": keep_mask is empty or names a locus slot beyond GRIM_MAXL");
-    return false;
-  }
-  if ((n && !res) || (n_rows && !rows) || n_rows > 0x7FFFFFFFu) {
-    set_err(m->ctx, std::string(who) + ": bad arguments");
-    return false;
-  }
-  return true;
-}
-
 extern "C" int grim_match_set_patients(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
   if (!m) return -1;
   grim_ctx *c = m->ctx;
   mt_clear(m);
   mt_drop_patients(m);
-  if (!mt_records_args_ok(m, "grim_match_set_patients", res, n, rows, n_rows)) return -3;
+  if (!records_door(c, "grim_match_set_patients", m->keep_mask, res, n, rows, n_rows)) return -3;
   if ((uint64_t)n > GRIM_MATCH_MAX_PAIRS) {
     set_err(c, "grim_match_set_patients: more patients than GRIM_MATCH_MAX_PAIRS");
     return -3;
   }
   use_device(c->device);
   if (n) {
-    if (mt_upload(m, "grim_match_set_patients", res, n, rows, n_rows) != 0) return -1;
+    if (m->in.upload(c, "grim_match_set_patients", res, n, rows, n_rows) != 0) return -1;
     HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MT_S_COUNT * MT_S_SLICES, c->stream), c, -1);
-    if (mt_prepare(m, "grim_match_set_patients", m->P, 0u, m->d_in_res, m->d_in_rows, n, n_rows) != 0) return -1;
+    if (mt_prepare(m, "grim_match_set_patients", m->P, 0u, m->in.res, m->in.rows, n, n_rows) != 0) return -1;
     uint32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, m->P.first + n, 4, hipMemcpyDeviceToHost, c->stream), c, -1);
-    if (mt_read_stat(m, m->pstat) != 0) return -1;
+    if (read_stat<MT_S_COUNT, MT_S_SLICES>(c, m->d_stat, m->pstat) != 0) return -1;
     if (total > n_rows) {  // regions that overlap: the kernel left those that did not fit alone
       mt_drop_patients(m);
       set_err(c, "grim_match_set_patients: the subjects' genotype rows overlap (more rows than there are)");
@@ -2448,31 +2387,26 @@ static int mt_run(grim_match *m, const char *who, const grim_subject_result *res
   if (n == 0) return 0;
   const uint32_t n_p = m->P.n;
   const uint64_t pairs = (uint64_t)n_p * n;
-  if (pairs + 1 > m->out_cap) {  // never an empty allocation
-    m->out_cap = 0;
-    if (!em_grow(m->d_out, (pairs + 1) * MT_REC)) {
-      set_err(c, std::string(who) + ": device allocation failed");
-      return -1;
-    }
-    m->out_cap = pairs + 1;
+  if (!m->d_out.reserve((pairs + 1) * MT_REC)) {  // never an empty allocation
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
   }
   HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MT_S_COUNT * MT_S_SLICES, st), c, -1);
   HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
   if (mt_prepare(m, who, m->D, 1u, res, rows, n, rows_used) != 0) return -1;
   if (pairs) {
     HIPCHK(hipMemsetAsync(m->d_out, 0, sizeof(double) * MT_REC * pairs, st), c, -1);  // a pair that is not computed reads as zero bytes
-    const MtSide P = {m->P.first, m->P.a, m->P.b, m->P.w, m->P.flags}, D = {m->D.first, m->D.a, m->D.b, m->D.w, m->D.flags};
-    for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {  // the grid's second dimension ends at 65535
-      const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+    const MtSide P = m->P.side(), D = m->D.side();
+    for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
       hipLaunchKernelGGL(mt_pair_kernel, dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, m->keep_mask, m->d_out, m->d_stat);
-    }
+    });
     HIPCHK(hipGetLastError(), c, -1);
   }
   HIPCHK(hipEventRecord(m->ev[1], st), c, -1);
   uint32_t total = 0;
   uint64_t h[MT_S_COUNT];
   HIPCHK(hipMemcpyAsync(&total, m->D.first + n, 4, hipMemcpyDeviceToHost, st), c, -1);
-  if (mt_read_stat(m, h) != 0) return -1;
+  if (read_stat<MT_S_COUNT, MT_S_SLICES>(c, m->d_stat, h) != 0) return -1;
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, m->ev[0], m->ev[1]), c, -1);
   if (total > rows_used) {
@@ -2486,14 +2420,8 @@ static int mt_run(grim_match *m, const char *who, const grim_subject_result *res
 }
 
 static bool mt_pairs_ok(grim_match *m, const char *who, uint32_t n) {
-  if (!m->have_patients) {
-    set_err(m->ctx, std::string(who) + ": no patients set (call grim_match_set_patients first)");
-    return false;
-  }
-  if ((uint64_t)m->P.n * n > GRIM_MATCH_MAX_PAIRS) {
-    set_err(m->ctx, std::string(who) + ": patients x donors above GRIM_MATCH_MAX_PAIRS");
-    return false;
-  }
+  if (!m->have_patients) return refuse(m->ctx, who, "no patients set (call grim_match_set_patients first)");
+  if ((uint64_t)m->P.n * n > GRIM_MATCH_MAX_PAIRS) return refuse(m->ctx, who, "patients x donors above GRIM_MATCH_MAX_PAIRS");
   return true;
 }
 
@@ -2501,22 +2429,7 @@ extern "C" int grim_match_run(grim_match *m, grim_batch *b) {
   if (!m || !b) return -1;
   grim_ctx *c = m->ctx;
   mt_clear(m);
-  if (b->ctx != c) {
-    set_err(c, "grim_match_run: the batch belongs to another context");
-    return -3;
-  }
-  if (!b->ran_ok) {
-    set_err(c, "grim_match_run: the batch holds no finished run (call grim_batch_run first)");
-    return -3;
-  }
-  if (!b->a.prm.out_muug) {
-    set_err(c, "grim_match_run: the batch was built with out_muug off: it holds no genotype rows");
-    return -3;
-  }
-  if (m->keep_mask == 0 || b->g->d.n_loci > GRIM_MAXL || (m->keep_mask >> b->g->d.n_loci) != 0) {
-    set_err(c, "grim_match_run: keep_mask is empty or names a locus slot the graph does not have");
-    return -3;
-  }
+  if (!batch_door(c, "grim_match_run", b, m->keep_mask, 0)) return -3;
   if (!mt_pairs_ok(m, "grim_match_run", b->n_subj)) return -3;
   use_device(c->device);
   return mt_run(m, "grim_match_run", b->a.res, b->a.rows, b->n_subj, b->rows_used);
@@ -2525,12 +2438,12 @@ extern "C" int grim_match_run(grim_match *m, grim_batch *b) {
 extern "C" int grim_match_run_records(grim_match *m, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
   if (!m) return -1;
   mt_clear(m);
-  if (!mt_records_args_ok(m, "grim_match_run_records", res, n, rows, n_rows)) return -3;
+  if (!records_door(m->ctx, "grim_match_run_records", m->keep_mask, res, n, rows, n_rows)) return -3;
   if (!mt_pairs_ok(m, "grim_match_run_records", n)) return -3;
   use_device(m->ctx->device);
   if (n == 0) return 0;
-  if (mt_upload(m, "grim_match_run_records", res, n, rows, n_rows) != 0) return -1;
-  return mt_run(m, "grim_match_run_records", m->d_in_res, m->d_in_rows, n, n_rows);
+  if (m->in.upload(m->ctx, "grim_match_run_records", res, n, rows, n_rows) != 0) return -1;
+  return mt_run(m, "grim_match_run_records", m->in.res, m->in.rows, n, n_rows);
 }
 
 extern "C" uint32_t grim_match_patients(const grim_match *m) { return m ? m->P.n : 0; }
@@ -2563,21 +2476,18 @@ struct grim_search {
   grim_match *m;  // owned; driven through the grim_match_* doors, whose behaviour is theirs
   uint32_t top_n, tile;
   double min_p0;
-  uint32_t *d_ids;
-  uint64_t ids_cap;
-  SrKey *d_keys[2];  // the lists of a level and of the next, in turns
-  uint32_t *d_cnt[2];
-  uint64_t keys_cap, cnt_cap;  // lists of top_n keys; counts
-  // the running list, double-buffered: run r reads [cur] and writes [cur ^ 1]
-  SrHit *d_hits[2];
-  SrKey *d_run_keys[2];
-  uint32_t *d_run_cnt[2];
-  uint64_t run_cap;  // patients
+  DevBuf<uint32_t> d_ids;
+  DevBuf<SrKey> d_keys[2];  // the lists of a level and of the next, in turns: top_n keys a list
+  DevBuf<uint32_t> d_cnt[2];
+  // the running list, double-buffered: run r reads [cur] and writes [cur ^ 1].  The six are reserved together, for the patients set.
+  DevBuf<SrHit> d_hits[2];
+  DevBuf<SrKey> d_run_keys[2];
+  DevBuf<uint32_t> d_run_cnt[2];
   int cur;
   bool have_running;  // [cur] holds lists (false: every list is empty, nothing on the device says so)
-  unsigned long long *d_cand;
+  DevBuf<unsigned long long> d_cand;
   uint64_t sum[8];  // the matcher's seven counters summed over the runs, [7] candidates
-  hipEvent_t ev[2];
+  Events<2> ev;
   double select_ms, kernel_ms;  // of the last run
 };
 
@@ -2620,9 +2530,7 @@ extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, cons
   s->top_n = top_n;
   s->tile = tile;
   s->min_p0 = min_p0;
-  bool ok = hipMalloc((void **)&s->d_cand, 8) == hipSuccess;
-  for (int k = 0; ok && k < 2; ++k) ok = hipEventCreate(&s->ev[k]) == hipSuccess;
-  if (!ok) {
+  if (!s->d_cand.reserve(1) || !s->ev.create()) {
     (void)hipGetLastError();
     set_err(c, "grim_search_create: device allocation failed");
     grim_search_free(s);
@@ -2635,14 +2543,9 @@ extern "C" void grim_search_free(grim_search *s) {
   if (!s) return;
   use_device(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
-  void *dev[] = {s->d_ids, s->d_keys[0], s->d_keys[1], s->d_cnt[0], s->d_cnt[1], s->d_hits[0], s->d_hits[1], s->d_run_keys[0],
-                 s->d_run_keys[1], s->d_run_cnt[0], s->d_run_cnt[1], s->d_cand};
-  for (void *p : dev)
-    if (p) hipFree(p);
-  for (int k = 0; k < 2; ++k)
-    if (s->ev[k]) hipEventDestroy(s->ev[k]);
-  grim_match_free(s->m);
-  delete s;
+  grim_match *m = s->m;
+  delete s;  // its own buffers first
+  grim_match_free(m);
 }
 
 extern "C" int grim_search_set_patients(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows) {
@@ -2667,27 +2570,14 @@ static int sr_select(grim_search *s, const char *who, const uint32_t *ids, uint3
   if (n == 0 || n_p == 0) return 0;
   const uint32_t tiles0 = (n + tile - 1) / tile;
   const uint64_t lists0 = (uint64_t)n_p * (tiles0 + 1ull);  // every level writes fewer lists than level 0
-  bool ok = true;
-  if ((uint64_t)n + 1 > s->ids_cap) {
-    s->ids_cap = 0;
-    if ((ok = em_grow(s->d_ids, (uint64_t)n + 1))) s->ids_cap = (uint64_t)n + 1;
+  bool ok = s->d_ids.reserve((uint64_t)n + 1) && reserve_all(lists0, 0, s->d_cnt[0], s->d_cnt[1]) &&
+            reserve_all(lists0 * top_n, 0, s->d_keys[0], s->d_keys[1]);
+  if (ok && s->have_running && (uint64_t)n_p > s->d_run_cnt[0].cap) {  // cannot be: the patients have not changed since the lists were made
+    set_err(c, std::string(who) + ": the running lists are smaller than the patients (internal)");  // growing would discard them
+    return -1;
   }
-  if (ok && lists0 > s->cnt_cap) {
-    s->cnt_cap = s->keys_cap = 0;
-    ok = em_grow(s->d_cnt[0], lists0) && em_grow(s->d_cnt[1], lists0) && em_grow(s->d_keys[0], lists0 * top_n) &&
-         em_grow(s->d_keys[1], lists0 * top_n);
-    if (ok) s->cnt_cap = lists0, s->keys_cap = lists0 * top_n;
-  }
-  if (ok && (uint64_t)n_p > s->run_cap) {
-    if (s->have_running) {  // cannot be: the patients have not changed since the lists were made
-      set_err(c, std::string(who) + ": the running lists are smaller than the patients (internal)");
-      return -1;
-    }
-    s->run_cap = 0;
-    for (int k = 0; ok && k < 2; ++k)
-      ok = em_grow(s->d_hits[k], (uint64_t)n_p * top_n) && em_grow(s->d_run_keys[k], (uint64_t)n_p * top_n) && em_grow(s->d_run_cnt[k], (uint64_t)n_p);
-    if (ok) s->run_cap = n_p;
-  }
+  ok = ok && reserve_all((uint64_t)n_p * top_n, 0, s->d_hits[0], s->d_hits[1], s->d_run_keys[0], s->d_run_keys[1]) &&
+       reserve_all(n_p, 0, s->d_run_cnt[0], s->d_run_cnt[1]);
   if (!ok) {
     set_err(c, std::string(who) + ": device allocation failed");
     return -1;
@@ -2696,34 +2586,32 @@ static int sr_select(grim_search *s, const char *who, const uint32_t *ids, uint3
   HIPCHK(hipMemsetAsync(s->d_cand, 0, 8, st), c, -1);
   HIPCHK(hipEventRecord(s->ev[0], st), c, -1);
   const int cur = s->cur, nxt = cur ^ 1;
-  const SrKey *extra = s->have_running ? s->d_run_keys[cur] : nullptr;
-  const uint32_t *extra_cnt = s->have_running ? s->d_run_cnt[cur] : nullptr;
+  const SrKey *extra = s->have_running ? s->d_run_keys[cur].p : nullptr;
+  const uint32_t *extra_cnt = s->have_running ? s->d_run_cnt[cur].p : nullptr;
+  const SrHit *hits_were = s->have_running ? s->d_hits[cur].p : nullptr;
   int side = 0;  // d_keys[side] holds the lists of the level just written
-  for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {  // the grid's second dimension ends at 65535
-    const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+  for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
     hipLaunchKernelGGL(sr_tile_kernel, dim3(tiles0, np), dim3(SR_THREADS), 0, st, m->d_out, s->d_ids, m->P.flags, m->D.flags, n_p, p0, n,
                        s->min_p0, (const SrKey *)nullptr, (const uint32_t *)nullptr, 0u, (const SrKey *)nullptr,
                        (const uint32_t *)nullptr, tile, top_n, s->d_keys[0], s->d_cnt[0], s->d_cand);
-  }
+  });
   uint32_t lists = tiles0;
   while (lists + (extra ? 1u : 0u) > 1u) {  // merging levels: per >= 2 lists become one
     const uint32_t out_lists = (lists + (extra ? 1u : 0u) + per - 1) / per;
-    for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {
-      const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
+    for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
       hipLaunchKernelGGL(sr_tile_kernel, dim3(out_lists, np), dim3(SR_THREADS), 0, st, (const double *)nullptr, (const uint32_t *)nullptr,
                          (const uint8_t *)nullptr, (const uint8_t *)nullptr, n_p, p0, 0u, s->min_p0, s->d_keys[side], s->d_cnt[side], lists,
                          extra, extra_cnt, tile, top_n, s->d_keys[side ^ 1], s->d_cnt[side ^ 1], s->d_cand);
-    }
+    });
     side ^= 1;
     lists = out_lists;
     extra = nullptr;
     extra_cnt = nullptr;
   }
-  for (uint32_t p0 = 0; p0 < n_p; p0 += 65535u) {
-    const uint32_t np = n_p - p0 < 65535u ? n_p - p0 : 65535u;
-    hipLaunchKernelGGL(sr_gather_kernel, dim3(np), dim3(64), 0, st, s->d_keys[side], s->d_cnt[side], lists, m->d_out, n_p, p0, n,
-                       s->have_running ? s->d_hits[cur] : (const SrHit *)nullptr, top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt]);
-  }
+  for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
+    hipLaunchKernelGGL(sr_gather_kernel, dim3(np), dim3(64), 0, st, s->d_keys[side], s->d_cnt[side], lists, m->d_out, n_p, p0, n, hits_were,
+                       top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt]);
+  });
   HIPCHK(hipGetLastError(), c, -1);
   HIPCHK(hipEventRecord(s->ev[1], st), c, -1);
   unsigned long long cand = 0;

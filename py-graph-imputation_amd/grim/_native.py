@@ -158,8 +158,40 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
-class Context:
+def _records(res, rows):
+    """host records -> (res RESULT_DT[n], rows ROW_DT[m], the four C arguments res, n, rows, m); the caller keeps the arrays
+    alive across the call"""
+    res = np.ascontiguousarray(res, dtype=RESULT_DT)
+    rows = np.ascontiguousarray(rows, dtype=ROW_DT)
+    return res, rows, (_ptr(res) if res.size else None, res.shape[0], _ptr(rows) if rows.size else None, rows.shape[0])
+
+
+class _Handle:
+    """an object of the library behind `h`, freed once by the function named `_free`; `ctx` holds its error text"""
+
+    _free = None
+    h = None
+
+    def _check(self, rc, name, code=True):
+        if rc != 0:
+            raise NativeError("%s failed%s: %s" % (name, " (%d)" % rc if code else "", self.ctx.error()))
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._free)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Context(_Handle):
     """One per GPU (grim_ctx)."""
+
+    _free = "grim_destroy"
 
     def __init__(self, device=0):
         L = lib()
@@ -174,17 +206,6 @@ class Context:
     def export_engine(self):
         """SDMA engine bit of the result downloads (> 1), 0 = copy kernel, -1 = hipMemcpyAsync (grim_export_engine)"""
         return int(lib().grim_export_engine(self.h))
-
-    def close(self):
-        if self.h:
-            lib().grim_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _contexts = {}
@@ -201,8 +222,10 @@ def default_context(device=None):
     return _contexts[device]
 
 
-class DeviceGraph:
+class DeviceGraph(_Handle):
     """Device-resident graph (grim_graph)."""
+
+    _free = "grim_graph_free"
 
     def __init__(self, ctx, arrays):
         L = lib()
@@ -226,20 +249,11 @@ class DeviceGraph:
     def device_bytes(self):
         return int(lib().grim_graph_device_bytes(self.h))
 
-    def close(self):
-        if self.h:
-            lib().grim_graph_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class DeviceBatch:
+class DeviceBatch(_Handle):
     """Subjects resident in HBM + result/scratch buffers (grim_batch)."""
+
+    _free = "grim_batch_free"
 
     def __init__(self, ctx, dgraph, params, subjects, tokens, priors):
         L = lib()
@@ -261,14 +275,10 @@ class DeviceBatch:
             raise NativeError("grim_batch_upload failed: " + ctx.error())
 
     def run(self):
-        rc = lib().grim_batch_run(self.h)
-        if rc != 0:
-            raise NativeError("grim_batch_run failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(lib().grim_batch_run(self.h), "grim_batch_run")
 
     def run_repeat(self, n):
-        rc = lib().grim_batch_run_repeat(self.h, int(n))
-        if rc != 0:
-            raise NativeError("grim_batch_run failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(lib().grim_batch_run_repeat(self.h, int(n)), "grim_batch_run")
 
     def set_timing(self, on=True):
         """start/stop hipEvents around every kernel of a run (resets the accumulated means); see grim_batch_set_timing"""
@@ -288,21 +298,8 @@ class DeviceBatch:
         nrows = int(L.grim_batch_total_rows(self.h))
         res = np.zeros(self.n, dtype=RESULT_DT)
         rows = np.zeros(max(nrows, 1), dtype=ROW_DT)
-        rc = L.grim_batch_results(self.h, _ptr(res), _ptr(rows))
-        if rc != 0:
-            raise NativeError("grim_batch_results failed: " + self.ctx.error())
+        self._check(L.grim_batch_results(self.h, _ptr(res), _ptr(rows)), "grim_batch_results", code=False)
         return res, rows[:nrows]
-
-    def close(self):
-        if self.h:
-            lib().grim_batch_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- M-step accumulator (grim_em_*): haplotype / population counts from the phased rows of finished batches ----
@@ -344,9 +341,11 @@ def _em_lib():
     return L
 
 
-class EmAccumulator:
+class EmAccumulator(_Handle):
     """grim_em: per-population haplotype counts summed on the device from the phased rows of finished batches, in input
     order and bit for bit independent of the batch cuts (include/grim_hip.h, the grim_em_* block)."""
+
+    _free = "grim_em_free"
 
     def __init__(self, ctx, n_alleles, n_pops, first_capacity=1 << 20):
         L = _em_lib()
@@ -359,9 +358,7 @@ class EmAccumulator:
 
     def accumulate(self, batch):
         """the counts of one DeviceBatch after its run(); synchronous"""
-        rc = _em_lib().grim_em_accumulate(self.h, batch.h)
-        if rc != 0:
-            raise NativeError("grim_em_accumulate failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(_em_lib().grim_em_accumulate(self.h, batch.h), "grim_em_accumulate")
 
     def entries(self):
         return int(_em_lib().grim_em_entries(self.h))
@@ -370,8 +367,8 @@ class EmAccumulator:
         """-> (keys u64, pops u32, counts f64), one element per (haplotype, population) counter, in (key, population) order"""
         n = self.entries()
         keys, pops, counts = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.float64)
-        if n and _em_lib().grim_em_export(self.h, _ptr(keys), _ptr(pops), _ptr(counts)) != 0:
-            raise NativeError("grim_em_export failed: " + self.ctx.error())
+        if n:
+            self._check(_em_lib().grim_em_export(self.h, _ptr(keys), _ptr(pops), _ptr(counts)), "grim_em_export", code=False)
         return keys, pops, counts
 
     def spill_count(self):
@@ -396,17 +393,6 @@ class EmAccumulator:
 
     def kernel_ms(self):
         return float(_em_lib().grim_em_kernel_ms(self.h))
-
-    def close(self):
-        if self.h:
-            _em_lib().grim_em_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- marginal genotype tables (grim_marginal_*): the UMUG rows of finished batches reduced to a subset of the loci ----
@@ -446,10 +432,12 @@ def _marginal_lib():
 MARGINAL_STATS = ("subjects", "rows_in", "groups", "rows_out", "undefined")
 
 
-class MarginalReducer:
+class MarginalReducer(_Handle):
     """grim_marginal: the genotype rows of a finished batch (or of host records) grouped on the kept locus slots, summed in
     rank order and ranked again, per subject, on the device (include/grim_hip.h, the grim_marginal_* block).  results(),
     stats() and kernel_ms() speak of the last reduce."""
+
+    _free = "grim_marginal_free"
 
     def __init__(self, ctx, keep_mask, max_rows):
         L = _marginal_lib()
@@ -460,18 +448,12 @@ class MarginalReducer:
 
     def reduce(self, batch):
         """one DeviceBatch after its run(), where its rows lie; synchronous"""
-        rc = _marginal_lib().grim_marginal_reduce(self.h, batch.h)
-        if rc != 0:
-            raise NativeError("grim_marginal_reduce failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(_marginal_lib().grim_marginal_reduce(self.h, batch.h), "grim_marginal_reduce")
 
     def reduce_records(self, res, rows):
         """host records (RESULT_DT[n], ROW_DT[m]) through the same kernels"""
-        res = np.ascontiguousarray(res, dtype=RESULT_DT)
-        rows = np.ascontiguousarray(rows, dtype=ROW_DT)
-        rc = _marginal_lib().grim_marginal_reduce_records(self.h, _ptr(res) if res.size else None, res.shape[0],
-                                                          _ptr(rows) if rows.size else None, rows.shape[0])
-        if rc != 0:
-            raise NativeError("grim_marginal_reduce_records failed (%d): %s" % (rc, self.ctx.error()))
+        res, rows, args = _records(res, rows)
+        self._check(_marginal_lib().grim_marginal_reduce_records(self.h, *args), "grim_marginal_reduce_records")
 
     def subjects(self):
         return int(_marginal_lib().grim_marginal_subjects(self.h))
@@ -485,8 +467,7 @@ class MarginalReducer:
         n, m = self.subjects(), self.total_rows()
         res = np.zeros(n, dtype=RESULT_DT)
         rows = np.zeros(max(m, 1), dtype=ROW_DT)
-        if L.grim_marginal_results(self.h, _ptr(res), _ptr(rows)) != 0:
-            raise NativeError("grim_marginal_results failed: " + self.ctx.error())
+        self._check(L.grim_marginal_results(self.h, _ptr(res), _ptr(rows)), "grim_marginal_results", code=False)
         return res, rows[:m]
 
     def stats(self):
@@ -496,17 +477,6 @@ class MarginalReducer:
 
     def kernel_ms(self):
         return float(_marginal_lib().grim_marginal_kernel_ms(self.h))
-
-    def close(self):
-        if self.h:
-            _marginal_lib().grim_marginal_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- match probabilities (grim_match_*): the UMUG rows of patients against those of finished batches of donors ----
@@ -551,10 +521,12 @@ def _match_lib():
     return L
 
 
-class Matcher:
+class Matcher(_Handle):
     """grim_match: for every (patient, donor) pair the probabilities of 0, 1, 2, ... mismatching alleles over the kept locus
     slots and the per-locus match probabilities, on the device (include/grim_hip.h, the grim_match_* block).  The patients
     stay set across runs; results(), stats() and kernel_ms() speak of the last run."""
+
+    _free = "grim_match_free"
 
     def __init__(self, ctx, keep_mask, n_alleles):
         L = _match_lib()
@@ -565,31 +537,19 @@ class Matcher:
         if not self.h:
             raise NativeError("grim_match_create failed: " + ctx.error())
 
-    @staticmethod
-    def _records(res, rows):
-        res = np.ascontiguousarray(res, dtype=RESULT_DT)
-        rows = np.ascontiguousarray(rows, dtype=ROW_DT)
-        return res, rows, (_ptr(res) if res.size else None, res.shape[0], _ptr(rows) if rows.size else None, rows.shape[0])
-
     def set_patients(self, res, rows):
         """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows"""
-        res, rows, args = self._records(res, rows)
-        rc = _match_lib().grim_match_set_patients(self.h, *args)
-        if rc != 0:
-            raise NativeError("grim_match_set_patients failed (%d): %s" % (rc, self.ctx.error()))
+        res, rows, args = _records(res, rows)
+        self._check(_match_lib().grim_match_set_patients(self.h, *args), "grim_match_set_patients")
 
     def run(self, batch):
         """one DeviceBatch after its run() as donors, where its rows lie; synchronous"""
-        rc = _match_lib().grim_match_run(self.h, batch.h)
-        if rc != 0:
-            raise NativeError("grim_match_run failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(_match_lib().grim_match_run(self.h, batch.h), "grim_match_run")
 
     def run_records(self, res, rows):
         """host records as donors, through the same kernels"""
-        res, rows, args = self._records(res, rows)
-        rc = _match_lib().grim_match_run_records(self.h, *args)
-        if rc != 0:
-            raise NativeError("grim_match_run_records failed (%d): %s" % (rc, self.ctx.error()))
+        res, rows, args = _records(res, rows)
+        self._check(_match_lib().grim_match_run_records(self.h, *args), "grim_match_run_records")
 
     def patients(self):
         return int(_match_lib().grim_match_patients(self.h))
@@ -602,9 +562,8 @@ class Matcher:
         n_p, n_d = self.patients(), self.donors()
         out = np.zeros((n_p, n_d), dtype=MATCH_DT)
         pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
-        if _match_lib().grim_match_results(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
-                                           _ptr(df) if n_d else None) != 0:
-            raise NativeError("grim_match_results failed: " + self.ctx.error())
+        self._check(_match_lib().grim_match_results(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
+                                                    _ptr(df) if n_d else None), "grim_match_results", code=False)
         return out, pf, df
 
     def stats(self):
@@ -614,17 +573,6 @@ class Matcher:
 
     def kernel_ms(self):
         return float(_match_lib().grim_match_kernel_ms(self.h))
-
-    def close(self):
-        if self.h:
-            _match_lib().grim_match_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- donor search (grim_search_*): each patient's best top_n donors over any number of runs, selected on the device ----
@@ -675,16 +623,17 @@ def _search_lib():
     return L
 
 
-class Searcher:
+class Searcher(_Handle):
     """grim_search: every patient's first top_n donors by match probability (mm[0] down, then mm[1] down, then id up) among the
     pairs with mm[0] >= min_p0, over all runs since the patients were set or the search was reset, selected on the device
     (include/grim_hip.h, the grim_search_* block).  results() and stats() speak of all runs so far; flags(), donors(),
     kernel_ms() and select_ms() of the last one."""
 
+    _free = "grim_search_free"
+
     def __init__(self, ctx, keep_mask, n_alleles, top_n, min_p0=0.0):
         L = _search_lib()
         self.ctx = ctx
-        self.h = None
         counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
         arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
         top_n = int(top_n)
@@ -703,30 +652,23 @@ class Searcher:
 
     def set_patients(self, res, rows):
         """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows; empties the hit lists"""
-        res, rows, args = Matcher._records(res, rows)
-        rc = _search_lib().grim_search_set_patients(self.h, *args)
-        if rc != 0:
-            raise NativeError("grim_search_set_patients failed (%d): %s" % (rc, self.ctx.error()))
+        res, rows, args = _records(res, rows)
+        self._check(_search_lib().grim_search_set_patients(self.h, *args), "grim_search_set_patients")
 
     def reset(self):
         """empties the hit lists and the summed statistics; the patients stay"""
-        if _search_lib().grim_search_reset(self.h) != 0:
-            raise NativeError("grim_search_reset failed: " + self.ctx.error())
+        self._check(_search_lib().grim_search_reset(self.h), "grim_search_reset", code=False)
 
     def run(self, batch, ids):
         """one DeviceBatch after its run() as donors, where its rows lie; ids: one uint32 per subject of the batch"""
         ids = self._ids(ids, batch.n)
-        rc = _search_lib().grim_search_run(self.h, batch.h, _ptr(ids) if ids.size else None)
-        if rc != 0:
-            raise NativeError("grim_search_run failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(_search_lib().grim_search_run(self.h, batch.h, _ptr(ids) if ids.size else None), "grim_search_run")
 
     def run_records(self, res, rows, ids):
         """host records as donors, through the same kernels"""
-        res, rows, args = Matcher._records(res, rows)
+        res, rows, args = _records(res, rows)
         ids = self._ids(ids, res.shape[0])
-        rc = _search_lib().grim_search_run_records(self.h, *args, _ptr(ids) if ids.size else None)
-        if rc != 0:
-            raise NativeError("grim_search_run_records failed (%d): %s" % (rc, self.ctx.error()))
+        self._check(_search_lib().grim_search_run_records(self.h, *args, _ptr(ids) if ids.size else None), "grim_search_run_records")
 
     def patients(self):
         return int(_search_lib().grim_search_patients(self.h))
@@ -742,16 +684,16 @@ class Searcher:
         n_p, top_n = self.patients(), self.top_n()
         hits = np.zeros((n_p, top_n), dtype=SEARCH_DT)
         n_hits = np.zeros(n_p, dtype=np.uint32)
-        if _search_lib().grim_search_results(self.h, _ptr(hits) if hits.size else None, _ptr(n_hits) if n_p else None) != 0:
-            raise NativeError("grim_search_results failed: " + self.ctx.error())
+        self._check(_search_lib().grim_search_results(self.h, _ptr(hits) if hits.size else None, _ptr(n_hits) if n_p else None),
+                    "grim_search_results", code=False)
         return hits, n_hits
 
     def flags(self):
         """-> (patient flags u8[patients], donor flags u8[donors of the last run])"""
         n_p, n_d = self.patients(), self.donors()
         pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
-        if _search_lib().grim_search_flags(self.h, _ptr(pf) if n_p else None, _ptr(df) if n_d else None) != 0:
-            raise NativeError("grim_search_flags failed: " + self.ctx.error())
+        self._check(_search_lib().grim_search_flags(self.h, _ptr(pf) if n_p else None, _ptr(df) if n_d else None), "grim_search_flags",
+                    code=False)
         return pf, df
 
     def stats(self):
@@ -764,17 +706,6 @@ class Searcher:
 
     def select_ms(self):
         return float(_search_lib().grim_search_select_ms(self.h))
-
-    def close(self):
-        if self.h:
-            _search_lib().grim_search_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ======================================================================================================
@@ -979,8 +910,10 @@ class AlleleDict:
             pass
 
 
-class Parsed:
+class Parsed(_Handle):
     """grim_parsed: a block of input lines tokenised by the library."""
+
+    _free = "grim_parsed_free"
 
     def __init__(self, adict, text_bytes, planb):
         L = host_lib()
@@ -1055,17 +988,6 @@ class Parsed:
                 out[key] = C.string_at(ptr, n.value).decode() if n.value else ""
         L.grim_text_free(t)
         return out
-
-    def close(self):
-        if self.h:
-            host_lib().grim_parsed_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def chunk_offsets(path, chunk_lines):
@@ -1181,6 +1103,15 @@ def prior_matrix(ps, pops, race1, race2):
     if rc != 0:
         raise NativeError("grim_prior_matrix failed")
     return out
+
+
+def prior_matrices(ps, pops, races):
+    """one prior matrix per race pair of `races` (Parsed.races()) -> float64[max(1, len(races))][P][P]; without a race pair
+    one matrix of ones"""
+    priors = np.ones((max(1, len(races)), len(pops), len(pops)))
+    for k, (r1, r2) in enumerate(races):
+        priors[k] = prior_matrix(ps, pops, r1, r2)
+    return priors
 
 
 TEXT_KEYS = ("umug", "umug_pops", "pmug", "pmug_pops", "miss", "problem")

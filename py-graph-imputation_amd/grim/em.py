@@ -20,9 +20,8 @@ bit.  There is no CPU fallback of `m_step_counts`.
 import gzip
 import os
 
-import numpy as np
-
 from . import _native as nat
+from .blocks import Blocks, note_unsupported, read_lines
 
 ALL_POPS = "all_pops"
 
@@ -79,70 +78,34 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
     pass left when that one ended in Plan C (impute.py:1637-1654), so the phased rows of some subjects differ with it off,
     and the counts are those of the rows the configured run prints.  -> ({pop: {haplotype: count}}, stats); the cuts do not show in any bit of a count.
     Subjects the device cannot answer follow `imputation.on_unsupported` as in `impute_lines_block`."""
-    from .imputation.impute import UnsupportedSubjects
-
-    if isinstance(lines_or_path, (str, bytes, os.PathLike)):
-        with open(lines_or_path) as fh:
-            lines = fh.read().splitlines()
-    else:
-        lines = [l.rstrip("\n") for l in lines_or_path]
-    if planb is None:
-        planb = config["planb"]
-    block_lines = max(1, int(block_lines))
+    lines = read_lines(lines_or_path)
     g = imputation.netGraph
     pops = imputation.populations
-    P = len(pops)
-    cfg = dict(config, output_haplotypes=True)
-    params = imputation._params(cfg, planb, True, em)
-    ps, keep = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
-    ctx = nat.default_context(imputation.device)
-    dgraph = g.device(ctx)
+    shared = Blocks(imputation, config, planb, True, em, output_haplotypes=True)
     n_slots = len(g.full_loci)
-    acc = nat.EmAccumulator(ctx, [g.adict.count(s) for s in range(n_slots)], P, first_capacity)
-    host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
+    acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(pops), first_capacity)
     imputation.unsupported = []
     spilled = {}  # (pop index, haplotype text) -> count: haplotypes that hold an allele the dictionary does not know
     kernel_ms = 0.0
     n_blocks = 0
+    cut = shared.cut(lines, max(1, int(block_lines)))
     try:
-        for lo in range(0, len(lines), block_lines):
-            text = "".join(l + "\n" for l in lines[lo:lo + block_lines]).encode()
-            parsed = nat.Parsed(g.adict, text, planb)
-            batch = None
-            try:
-                kinds = parsed.kinds()
-                dev = parsed.dev_index()
-                bad = [(lo + int(j), parsed.subject_id(int(j)), host_reason[int(kinds[j])]) for j in np.flatnonzero(np.isin(kinds, list(host_reason)))]
-                subj = parsed.subjects()
-                if len(subj):
-                    races = parsed.races()
-                    priors = np.ones((max(1, len(races)), P, P))
-                    for k, (r1, r2) in enumerate(races):
-                        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
-                    batch = nat.DeviceBatch(ctx, dgraph, params, subj, parsed.tokens(), priors)
-                    batch.run()
-                    seen = acc.spill_count()
-                    acc.accumulate(batch)
-                    kernel_ms += acc.kernel_ms()
-                    n_blocks += 1
-                    line_of = {int(dev[j]): int(j) for j in np.flatnonzero(kinds == nat.K_DEVICE)}
-                    if acc.last_unsupported():
-                        res, _ = batch.results()
-                        bad += [(lo + line_of[int(i)], parsed.subject_id(line_of[int(i)]), int(res[i]["reason"]))
-                                for i in np.flatnonzero(res["status"] == nat.ST_UNSUPPORTED)]
-                    for rec in acc.spill(seen):
-                        line, key = line_of[int(rec["subject"])], int(rec["key"])
-                        fields = [(s, (key >> (nat.ABITS * s)) & 0xFFF) for s in range(n_slots)]
-                        name = "~".join(parsed.allele(line, s, a - 1) for s, a in fields if a)
-                        at = (int(rec["pop"]), name)
-                        spilled[at] = spilled[at] + float(rec["w"]) if at in spilled else float(rec["w"])
-                imputation.unsupported += sorted(bad)
-                if imputation.unsupported and imputation.on_unsupported == "raise":
-                    raise UnsupportedSubjects(imputation.unsupported)
-            finally:
-                if batch is not None:
-                    batch.close()
-                parsed.close()
+        for block in cut:
+            bad = block.bad
+            if block.batch is not None:
+                seen = acc.spill_count()
+                acc.accumulate(block.batch)
+                kernel_ms += acc.kernel_ms()
+                n_blocks += 1
+                if acc.last_unsupported():
+                    bad = bad + block.unsupported()
+                for rec in acc.spill(seen):
+                    line, key = int(block.line_of[int(rec["subject"])]), int(rec["key"])
+                    fields = [(s, (key >> (nat.ABITS * s)) & 0xFFF) for s in range(n_slots)]
+                    name = "~".join(block.parsed.allele(line, s, a - 1) for s, a in fields if a)
+                    at = (int(rec["pop"]), name)
+                    spilled[at] = spilled[at] + float(rec["w"]) if at in spilled else float(rec["w"])
+            note_unsupported(imputation, bad)
         keys, kpops, vals = acc.export()
         counts = {}
         names = {}
@@ -156,6 +119,7 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
         stats = acc.stats()
         stats.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
     finally:
+        cut.close()
         acc.close()
     return counts, stats
 

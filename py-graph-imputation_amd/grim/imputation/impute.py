@@ -19,6 +19,7 @@ import timeit
 import numpy as np
 
 from .. import _native as nat
+from ..blocks import host_reason
 
 # outcome of tokenising one input line
 _DEV, _PROBLEM_ID, _PROBLEM_RAW, _MISS_NO_DEVICE, _UNSUPPORTED_GL = 0, 1, 2, 3, 5
@@ -568,12 +569,8 @@ class Imputation(object):
         text = "".join(l if l.endswith("\n") else l + "\n" for l in lines).encode()
         parsed = nat.Parsed(self.netGraph.adict, text, planb)
         try:
-            races = parsed.races()
-            P = len(self.populations)
             ps, keep = nat.prior_spec(priority, self.unk_priors, self.count_by_prob)
-            priors = np.ones((max(1, len(races)), P, P))
-            for k, (r1, r2) in enumerate(races):
-                priors[k] = nat.prior_matrix(ps, self.populations, r1, r2)
+            priors = nat.prior_matrices(ps, self.populations, parsed.races())
             subj = parsed.subjects()
             kinds = parsed.kinds()
             dev = parsed.dev_index()
@@ -582,7 +579,6 @@ class Imputation(object):
                 res, rows = self._run_arrays(subj, parsed.tokens(), priors, params)
             else:
                 res, rows = np.zeros(0, dtype=nat.RESULT_DT), np.zeros(0, dtype=nat.ROW_DT)
-            host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
             bad_lines = [int(j) for j in range(len(kinds)) if kinds[j] in host_reason or
                          (kinds[j] == nat.K_DEVICE and res["status"][dev[j]] == nat.ST_UNSUPPORTED)]
             self.unsupported = [(line_offset + j, parsed.subject_id(j), host_reason[kinds[j]] if kinds[j] in host_reason else int(res[dev[j]]["reason"]))

@@ -21,11 +21,10 @@ merges every input line that shares an id, wherever it stands), and `max_rows` d
 `number_of_results` (the script hard-codes 10).
 """
 
-import os
-
 import numpy as np
 
 from . import _native as nat
+from .blocks import Blocks, note_unsupported, read_lines
 
 
 def keep_mask(locus_slot, keep_loci):
@@ -147,76 +146,41 @@ def marginal_umug(imputation, lines_or_path, config, keep_loci, max_rows=None, b
     is tokenised, imputed as one device batch (genotype output on, the rest as configured), reduced where its rows lie, and
     the reduced records are printed by the formatter of every other text.  -> (text, stats); the cuts do not show in any
     byte.  Subjects the device cannot answer follow `imputation.on_unsupported` as in `impute_lines_block`."""
-    from .imputation.impute import UnsupportedSubjects
-
     g = imputation.netGraph
     mask = keep_mask(g.locus_slot, keep_loci)
     if max_rows is None:
         max_rows = int(config["number_of_results"])
     if int(max_rows) < 1:
         raise ValueError("max_rows must be at least 1")
-    if isinstance(lines_or_path, (str, bytes, os.PathLike)):
-        with open(lines_or_path) as fh:
-            lines = fh.read().splitlines()
-    else:
-        lines = [l.rstrip("\n") for l in lines_or_path]
-    if planb is None:
-        planb = config["planb"]
-    block_lines = max(1, int(block_lines))
-    pops = imputation.populations
-    P = len(pops)
-    cfg = dict(config, output_MUUG=True)
-    params = imputation._params(cfg, planb, False, em)
-    fparams = nat.Params.from_buffer_copy(params)  # what the formatter is told: genotype rows only
+    lines = read_lines(lines_or_path)
+    shared = Blocks(imputation, config, planb, False, em, output_MUUG=True)
+    fparams = nat.Params.from_buffer_copy(shared.params)  # what the formatter is told: genotype rows only
     fparams.out_muug, fparams.out_haps = 1, 0
-    ps, keep = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
-    ctx = nat.default_context(imputation.device)
-    dgraph = g.device(ctx)
-    red = nat.MarginalReducer(ctx, mask, max_rows)
-    host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
+    red = nat.MarginalReducer(shared.ctx, mask, max_rows)
     imputation.unsupported = []
     stats = dict.fromkeys(nat.MARGINAL_STATS, 0)
     stats.update(blocks=0, kernel_ms=0.0)
     out = []
+    cut = shared.cut(lines, max(1, int(block_lines)))
     try:
-        for lo in range(0, len(lines), block_lines):
-            text = "".join(l + "\n" for l in lines[lo:lo + block_lines]).encode()
-            parsed = nat.Parsed(g.adict, text, planb)
-            batch = None
-            try:
-                kinds = parsed.kinds()
-                dev = parsed.dev_index()
-                bad = [(lo + int(j), parsed.subject_id(int(j)), host_reason[int(kinds[j])]) for j in np.flatnonzero(np.isin(kinds, list(host_reason)))]
-                subj = parsed.subjects()
-                mres, mrows = np.zeros(0, dtype=nat.RESULT_DT), np.zeros(0, dtype=nat.ROW_DT)
-                if len(subj):
-                    races = parsed.races()
-                    priors = np.ones((max(1, len(races)), P, P))
-                    for k, (r1, r2) in enumerate(races):
-                        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
-                    batch = nat.DeviceBatch(ctx, dgraph, params, subj, parsed.tokens(), priors)
-                    batch.run()
-                    red.reduce(batch)
-                    for k, v in red.stats().items():
-                        stats[k] += v
-                    stats["kernel_ms"] += red.kernel_ms()
-                    stats["blocks"] += 1
-                    mres, mrows = red.results()
-                    line_of = {int(dev[j]): int(j) for j in np.flatnonzero(kinds == nat.K_DEVICE)}
-                    bad += [(lo + line_of[int(i)], parsed.subject_id(line_of[int(i)]), int(mres[i]["reason"]))
-                            for i in np.flatnonzero(mres["status"] == nat.ST_UNSUPPORTED)]
-                imputation.unsupported += sorted(bad)
-                if imputation.unsupported and imputation.on_unsupported == "raise":
-                    raise UnsupportedSubjects(imputation.unsupported)
-                if stats["undefined"]:
-                    raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their "
-                                     "marginal is not defined" % stats["undefined"])
-                out.append(parsed.format(g.adict, fparams, pops, mres, mrows, lo, None)["umug"])
-            finally:
-                if batch is not None:
-                    batch.close()
-                parsed.close()
+        for block in cut:
+            bad = block.bad
+            mres, mrows = np.zeros(0, dtype=nat.RESULT_DT), np.zeros(0, dtype=nat.ROW_DT)
+            if block.batch is not None:
+                red.reduce(block.batch)
+                for k, v in red.stats().items():
+                    stats[k] += v
+                stats["kernel_ms"] += red.kernel_ms()
+                stats["blocks"] += 1
+                mres, mrows = red.results()
+                bad = bad + block.unsupported(mres)  # the reduced records carry the batch's status and reason
+            note_unsupported(imputation, bad)
+            if stats["undefined"]:
+                raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their "
+                                 "marginal is not defined" % stats["undefined"])
+            out.append(block.parsed.format(g.adict, fparams, imputation.populations, mres, mrows, block.lo, None)["umug"])
     finally:
+        cut.close()
         red.close()
     return "".join(out), stats
 

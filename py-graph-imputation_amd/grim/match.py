@@ -24,11 +24,11 @@ fallback of the device functions.
 """
 
 import math
-import os
 
 import numpy as np
 
 from . import _native as nat
+from .blocks import Blocks, note_unsupported, read_lines
 from .marginal import keep_mask as _keep_mask
 
 
@@ -242,59 +242,86 @@ def text_records_array(records, locus_slot):
     return out
 
 
-class _Block:
-    """a block of input lines tokenised and imputed as one device batch (genotype output on); the caller closes it"""
+class _Pairing:
+    """What match_probabilities and search_donors share: the patients imputed as one block and set on the device object (a
+    Matcher or a Searcher), the donors cut into blocks, the check of a block's flags, and the host fold of the pairs the
+    device leaves out.  The callers run each donor block themselves and do what they like with the pairs."""
 
-    def __init__(self, imputation, ctx, dgraph, params, ps, lines, lo, planb):
-        g = imputation.netGraph
-        pops = imputation.populations
-        host_reason = {nat.K_UNSUPPORTED: 5, nat.K_UNSUPPORTED_GL: 8}
-        self.lo = lo
-        self.batch = None
-        self.parsed = nat.Parsed(g.adict, "".join(l + "\n" for l in lines).encode(), planb)
-        try:
-            kinds = self.parsed.kinds()
-            dev = self.parsed.dev_index()
-            self.bad = [(lo + int(j), self.parsed.subject_id(int(j)), host_reason[int(kinds[j])])
-                        for j in np.flatnonzero(np.isin(kinds, list(host_reason)))]
-            on_dev = np.flatnonzero(kinds == nat.K_DEVICE)
-            self.line_of = np.zeros(self.parsed.n_subjects, dtype=np.int64)  # device subject -> line of the block
-            self.line_of[dev[on_dev]] = on_dev
-            subj = self.parsed.subjects()
-            if len(subj):
-                races = self.parsed.races()
-                priors = np.ones((max(1, len(races)), len(pops), len(pops)))
-                for k, (r1, r2) in enumerate(races):
-                    priors[k] = nat.prior_matrix(ps, pops, r1, r2)
-                self.batch = nat.DeviceBatch(ctx, dgraph, params, subj, self.parsed.tokens(), priors)
-                self.batch.run()
-        except BaseException:
-            self.close()
-            raise
-        self._records = None
+    def __init__(self, imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em):
+        self.imputation = imputation
+        self.g = g = imputation.netGraph
+        self.mask = _keep_mask(g.locus_slot, keep_loci)
+        self.slots = _slots_of(self.mask)
+        self.dlines = read_lines(donor_lines_or_path)
+        self.plines = [l.rstrip("\n") for l in patient_lines]
+        if len(self.plines) > nat.MATCH_MAX_PAIRS:
+            raise ValueError("%d patients: more than %d pairs with a single donor" % (len(self.plines), nat.MATCH_MAX_PAIRS))
+        self.block_lines = max(1, min(int(block_lines), nat.MATCH_MAX_PAIRS // max(1, len(self.plines))))
+        self.blocks = Blocks(imputation, config, planb, False, em, output_MUUG=True)
+        self.ctx = self.blocks.ctx
+        self.n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))] + [0] * (nat.MAXL - len(g.full_loci))
+        self.folder = _Folder(len(self.slots))  # of the text route
+        self.patient_ok = np.zeros(len(self.plines), dtype=bool)
+        self.pblock = self._cut = None
+        self.pf = np.zeros(0, dtype=np.uint8)
+        self.ptext = {}  # patient -> its rows on allele text
+        imputation.unsupported = []
 
-    def records(self):
-        if self._records is None:
-            self._records = self.batch.results()
-        return self._records
+    def set_patients(self, dev, patient_flags, stats):
+        """the patients as one block onto `dev`; `patient_flags`: () -> their flags on the device.  Their batch is closed as
+        soon as they are set: the records are on the host, the patients prepared on the device; the tokenised lines stay for
+        the text route."""
+        self.pblock = self.blocks.block(self.plines)
+        if self.pblock.batch is not None:
+            dev.set_patients(*self.pblock.records())
+            self.pf = patient_flags()
+            self.pblock.batch.close()
+        self.check(self.pblock, self.pf)
+        self.patient_ok[self.pblock.line_of[np.flatnonzero(self.pf & nat.MATCH_VALID)]] = True
+        stats["patients_valid"] = int(np.count_nonzero(self.pf & nat.MATCH_VALID))
+        stats["patients_private"] = int(np.count_nonzero(self.pf & nat.MATCH_PRIVATE))
 
-    def unsupported(self):
-        res, _ = self.records()
-        return [(self.lo + int(self.line_of[i]), self.parsed.subject_id(int(self.line_of[i])), int(res[i]["reason"]))
-                for i in np.flatnonzero(res["status"] == nat.ST_UNSUPPORTED)]
+    def donor_blocks(self):
+        self._cut = self.blocks.cut(self.dlines, self.block_lines)
+        return self._cut
 
-    def text_subject(self, g, i, slots, n_alleles, folder):
-        """device subject i's rows on allele text -> (packed genotypes, weights)"""
-        res, rows = self.records()
+    def check(self, block, flags):
+        """a block after its run: its unsupported subjects noted (the records are fetched for them only when some subject
+        has no flag at all), and no subject's match undefined"""
+        note_unsupported(self.imputation, block.bad + (block.unsupported() if block.batch is not None and not flags.all() else []))
+        if np.count_nonzero(flags & nat.MATCH_UNDEFINED):
+            raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their match is "
+                             "not defined" % np.count_nonzero(flags & nat.MATCH_UNDEFINED))
+
+    def host_pairs(self, block, df):
+        """a donor block after its run, `df` its flags: checks it, then yields (p, d, H, L) for every pair of valid subjects
+        the device left out for a private allele: the same fold on allele text"""
+        self.check(block, df)
+        ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
+        pf, ptext, dtext = self.pf, self.ptext, {}
+        for p in np.flatnonzero(pf & nat.MATCH_VALID):
+            for d in np.flatnonzero(df & nat.MATCH_VALID):
+                if (pf[p] & ready) == nat.MATCH_VALID and (df[d] & ready) == nat.MATCH_VALID:
+                    continue
+                if p not in ptext:
+                    ptext[p] = self._text_subject(self.pblock, int(p))
+                if d not in dtext:
+                    dtext[d] = self._text_subject(block, int(d))
+                H, L = self.folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
+                yield p, d, H, L
+
+    def _text_subject(self, block, i):
+        """device subject i of `block`: its rows on allele text -> (packed genotypes, weights)"""
+        res, rows = block.records()
         n, off = int(res[i]["n_rows"][nat.T_UMUG]), int(res[i]["row_off"][nat.T_UMUG])
-        line = int(self.line_of[i])
+        line = int(block.line_of[i])
         names = {}
 
         def text(s, f):
             if f == 0:
                 return None
             if (s, f) not in names:  # an id above the dictionary's is the line's own
-                names[(s, f)] = self.parsed.allele(line, s, f - 1) if f > n_alleles[s] else g.key_alleles(f << (nat.ABITS * s))[s]
+                names[(s, f)] = block.parsed.allele(line, s, f - 1) if f > self.n_alleles[s] else self.g.key_alleles(f << (nat.ABITS * s))[s]
             return names[(s, f)]
 
         ps = [float(rows[off + k]["prob"]) for k in range(n)]
@@ -302,14 +329,14 @@ class _Block:
         genos = []
         for k in range(n):
             a, b = int(rows[off + k]["a"]), int(rows[off + k]["b"])
-            genos.append(tuple((text(s, (a >> (nat.ABITS * s)) & 0xFFF), text(s, (b >> (nat.ABITS * s)) & 0xFFF)) for s in slots))
-        return folder.pack(genos), [p / total for p in ps]
+            genos.append(tuple((text(s, (a >> (nat.ABITS * s)) & 0xFFF), text(s, (b >> (nat.ABITS * s)) & 0xFFF)) for s in self.slots))
+        return self.folder.pack(genos), [p / total for p in ps]
 
     def close(self):
-        if self.batch is not None:
-            self.batch.close()
-            self.batch = None
-        self.parsed.close()
+        if self._cut is not None:
+            self._cut.close()
+        if self.pblock is not None:
+            self.pblock.close()
 
 
 def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines=65536, planb=None, em=False):
@@ -323,96 +350,35 @@ def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, 
     lines)], zero for lines without genotype rows; *_ok say which lines have them; stats adds `blocks`, `kernel_ms` and
     `host_pairs` (pairs folded on text).  The cuts do not show in any byte.  Subjects the device cannot answer follow
     `imputation.on_unsupported` as in `impute_lines_block`."""
-    from .imputation.impute import UnsupportedSubjects
-
-    g = imputation.netGraph
-    mask = _keep_mask(g.locus_slot, keep_loci)
-    slots = _slots_of(mask)
-    if isinstance(donor_lines_or_path, (str, bytes, os.PathLike)):
-        with open(donor_lines_or_path) as fh:
-            dlines = fh.read().splitlines()
-    else:
-        dlines = [l.rstrip("\n") for l in donor_lines_or_path]
-    plines = [l.rstrip("\n") for l in patient_lines]
-    if len(plines) > nat.MATCH_MAX_PAIRS:
-        raise ValueError("%d patients: more than %d pairs with a single donor" % (len(plines), nat.MATCH_MAX_PAIRS))
-    if planb is None:
-        planb = config["planb"]
-    block_lines = max(1, min(int(block_lines), nat.MATCH_MAX_PAIRS // max(1, len(plines))))
-    cfg = dict(config, output_MUUG=True)
-    params = imputation._params(cfg, planb, False, em)
-    ps, _ = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
-    ctx = nat.default_context(imputation.device)
-    dgraph = g.device(ctx)
-    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))] + [0] * (nat.MAXL - len(g.full_loci))
-    matcher = nat.Matcher(ctx, mask, n_alleles)
-    imputation.unsupported = []
+    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em)
+    matcher = nat.Matcher(pairing.ctx, pairing.mask, pairing.n_alleles)
     stats = dict.fromkeys(nat.MATCH_STATS, 0)
     stats.update(blocks=0, kernel_ms=0.0, host_pairs=0)
-    out = np.zeros((len(plines), len(dlines)), dtype=nat.MATCH_DT)
-    patient_ok, donor_ok = np.zeros(len(plines), dtype=bool), np.zeros(len(dlines), dtype=bool)
-    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
-    folder = _Folder(len(slots))  # of the text route
-    pblock = None
-
-    def check(block, flags):
-        bad = block.bad + (block.unsupported() if block.batch is not None and not flags.all() else [])
-        imputation.unsupported += sorted(bad)
-        if imputation.unsupported and imputation.on_unsupported == "raise":
-            raise UnsupportedSubjects(imputation.unsupported)
-        if np.count_nonzero(flags & nat.MATCH_UNDEFINED):
-            raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their match is "
-                             "not defined" % np.count_nonzero(flags & nat.MATCH_UNDEFINED))
-
+    out = np.zeros((len(pairing.plines), len(pairing.dlines)), dtype=nat.MATCH_DT)
+    donor_ok = np.zeros(len(pairing.dlines), dtype=bool)
     try:
-        pblock = _Block(imputation, ctx, dgraph, params, ps, plines, 0, planb)
-        pf = np.zeros(0, dtype=np.uint8)
-        if pblock.batch is not None:
-            matcher.set_patients(*pblock.records())
-            pf = matcher.results()[1]
-            pblock.batch.close()  # the records are on the host, the patients prepared on the device
-        check(pblock, pf)
-        patient_ok[pblock.line_of[np.flatnonzero(pf & nat.MATCH_VALID)]] = True
-        stats["patients_valid"] = int(np.count_nonzero(pf & nat.MATCH_VALID))
-        stats["patients_private"] = int(np.count_nonzero(pf & nat.MATCH_PRIVATE))
-        ptext = {}  # patient -> its rows on allele text
-        for lo in range(0, len(dlines), block_lines):
-            block = _Block(imputation, ctx, dgraph, params, ps, dlines[lo:lo + block_lines], lo, planb)
-            try:
-                if block.batch is None:
-                    check(block, np.zeros(0, dtype=np.uint8))
-                    continue
-                matcher.run(block.batch)
-                rec, _, df = matcher.results()
-                run = matcher.stats()
-                check(block, df)
-                for k in ("donors_valid", "donors_private", "pairs", "row_pairs"):
-                    stats[k] += run[k]
-                stats["kernel_ms"] += matcher.kernel_ms()
-                stats["blocks"] += 1
-                donor_ok[lo + block.line_of[np.flatnonzero(df & nat.MATCH_VALID)]] = True
-                # pairs the device left out for a private allele: the same fold on allele text
-                dtext = {}
-                for p in np.flatnonzero(pf & nat.MATCH_VALID):
-                    for d in np.flatnonzero(df & nat.MATCH_VALID):
-                        if (pf[p] & ready) == nat.MATCH_VALID and (df[d] & ready) == nat.MATCH_VALID:
-                            continue
-                        if p not in ptext:
-                            ptext[p] = pblock.text_subject(g, int(p), slots, n_alleles, folder)
-                        if d not in dtext:
-                            dtext[d] = block.text_subject(g, int(d), slots, n_alleles, folder)
-                        H, L = folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
-                        _store(rec[p, d], slots, H, L)
-                        stats["host_pairs"] += 1
-                if len(pf):
-                    out[pblock.line_of[:, None], lo + block.line_of[None, :]] = rec
-            finally:
-                block.close()
+        pairing.set_patients(matcher, lambda: matcher.results()[1], stats)
+        for block in pairing.donor_blocks():
+            if block.batch is None:
+                pairing.check(block, np.zeros(0, dtype=np.uint8))
+                continue
+            matcher.run(block.batch)
+            rec, _, df = matcher.results()
+            run = matcher.stats()
+            for p, d, H, L in pairing.host_pairs(block, df):
+                _store(rec[p, d], pairing.slots, H, L)
+                stats["host_pairs"] += 1
+            for k in ("donors_valid", "donors_private", "pairs", "row_pairs"):
+                stats[k] += run[k]
+            stats["kernel_ms"] += matcher.kernel_ms()
+            stats["blocks"] += 1
+            donor_ok[block.lo + block.line_of[np.flatnonzero(df & nat.MATCH_VALID)]] = True
+            if len(pairing.pf):
+                out[pairing.pblock.line_of[:, None], block.lo + block.line_of[None, :]] = rec
     finally:
-        if pblock is not None:
-            pblock.close()
+        pairing.close()
         matcher.close()
-    return patient_ok, donor_ok, out, stats
+    return pairing.patient_ok, donor_ok, out, stats
 
 
 def line_id(line):
@@ -434,10 +400,7 @@ def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0
     if graph is None:
         graph = graph_instance(config)
     imp = Imputation(graph, config)
-    with open(patients_path) as fh:
-        plines = fh.read().splitlines()
-    with open(config["imputation_input_file"]) as fh:
-        dlines = fh.read().splitlines()
+    plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
     pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines)
     slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
     nb = 2 * len(slots) + 1

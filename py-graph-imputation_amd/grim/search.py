@@ -20,12 +20,12 @@ bit for bit.  There is no CPU fallback of the device functions.
 """
 
 import math
-import os
 
 import numpy as np
 
 from . import _native as nat
-from .match import _Block, _Folder, _keep_mask, _slots_of, _store, line_id, match_records, match_umug_text
+from .blocks import read_lines
+from .match import _Pairing, _keep_mask, _slots_of, _store, line_id, match_records, match_umug_text
 
 
 def _check(top_n, min_p0):
@@ -107,99 +107,40 @@ def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_l
     `select_ms`, `host_pairs` (pairs folded on text) and `download_bytes` (hits and counts fetched from the device).  The cuts
     do not show in any byte.  Subjects the device cannot answer follow `imputation.on_unsupported` as in
     `impute_lines_block`."""
-    from .imputation.impute import UnsupportedSubjects
-
     top_n, min_p0 = _check(top_n, min_p0)
-    g = imputation.netGraph
-    mask = _keep_mask(g.locus_slot, keep_loci)
-    slots = _slots_of(mask)
-    if isinstance(donor_lines_or_path, (str, bytes, os.PathLike)):
-        with open(donor_lines_or_path) as fh:
-            dlines = fh.read().splitlines()
-    else:
-        dlines = [l.rstrip("\n") for l in donor_lines_or_path]
-    plines = [l.rstrip("\n") for l in patient_lines]
-    if len(plines) > nat.MATCH_MAX_PAIRS:
-        raise ValueError("%d patients: more than %d pairs with a single donor" % (len(plines), nat.MATCH_MAX_PAIRS))
-    if len(dlines) >= nat.SEARCH_NO_DONOR:
-        raise ValueError("%d donor lines: a line number must fit a hit's donor field" % len(dlines))
-    if planb is None:
-        planb = config["planb"]
-    block_lines = max(1, min(int(block_lines), nat.MATCH_MAX_PAIRS // max(1, len(plines))))
-    cfg = dict(config, output_MUUG=True)
-    params = imputation._params(cfg, planb, False, em)
-    ps, _ = nat.prior_spec(config["priority"], imputation.unk_priors, imputation.count_by_prob)
-    ctx = nat.default_context(imputation.device)
-    dgraph = g.device(ctx)
-    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))] + [0] * (nat.MAXL - len(g.full_loci))
-    searcher = nat.Searcher(ctx, mask, n_alleles, top_n, min_p0)
-    imputation.unsupported = []
+    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em)
+    plines, slots = pairing.plines, pairing.slots
+    if len(pairing.dlines) >= nat.SEARCH_NO_DONOR:
+        raise ValueError("%d donor lines: a line number must fit a hit's donor field" % len(pairing.dlines))
+    searcher = nat.Searcher(pairing.ctx, pairing.mask, pairing.n_alleles, top_n, min_p0)
     stats = dict.fromkeys(nat.SEARCH_STATS, 0)
     stats.update(blocks=0, kernel_ms=0.0, select_ms=0.0, host_pairs=0, download_bytes=0)
     hits = _empty_hits(len(plines), top_n)
     n_hits = np.zeros(len(plines), dtype=np.uint32)
-    patient_ok = np.zeros(len(plines), dtype=bool)
-    ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
-    folder = _Folder(len(slots))  # of the text route
-    pblock = None
-
-    def check(block, flags):
-        bad = block.bad + (block.unsupported() if block.batch is not None and not flags.all() else [])
-        imputation.unsupported += sorted(bad)
-        if imputation.unsupported and imputation.on_unsupported == "raise":
-            raise UnsupportedSubjects(imputation.unsupported)
-        if np.count_nonzero(flags & nat.MATCH_UNDEFINED):
-            raise ValueError("%d subject(s) hold a genotype row whose haplotypes are typed at different loci: their match is "
-                             "not defined" % np.count_nonzero(flags & nat.MATCH_UNDEFINED))
-
     try:
-        pblock = _Block(imputation, ctx, dgraph, params, ps, plines, 0, planb)
-        pf = np.zeros(0, dtype=np.uint8)
-        if pblock.batch is not None:
-            searcher.set_patients(*pblock.records())
-            pf = searcher.flags()[0]
-            pblock.batch.close()  # the records are on the host, the patients prepared on the device
-        check(pblock, pf)
-        patient_ok[pblock.line_of[np.flatnonzero(pf & nat.MATCH_VALID)]] = True
-        stats["patients_valid"] = int(np.count_nonzero(pf & nat.MATCH_VALID))
-        stats["patients_private"] = int(np.count_nonzero(pf & nat.MATCH_PRIVATE))
-        ptext = {}  # patient -> its rows on allele text
+        pairing.set_patients(searcher, lambda: searcher.flags()[0], stats)
+        pf, pblock = pairing.pf, pairing.pblock
         host = {}   # patient -> [((-mm0, -mm1, id), H, L)] of the pairs folded here, at most top_n after a block
-        for lo in range(0, len(dlines), block_lines):
-            block = _Block(imputation, ctx, dgraph, params, ps, dlines[lo:lo + block_lines], lo, planb)
-            try:
-                if block.batch is None or not len(pf):
-                    check(block, np.zeros(0, dtype=np.uint8))
-                    continue
-                ids = lo + block.line_of
-                searcher.run(block.batch, ids.astype(np.uint32))
-                df = searcher.flags()[1]
-                check(block, df)
-                stats["donors_valid"] += int(np.count_nonzero(df & nat.MATCH_VALID))
-                stats["donors_private"] += int(np.count_nonzero(df & nat.MATCH_PRIVATE))
-                stats["kernel_ms"] += searcher.kernel_ms()
-                stats["select_ms"] += searcher.select_ms()
-                stats["blocks"] += 1
-                # pairs the device left out for a private allele: the same fold on allele text
-                dtext = {}
-                for p in np.flatnonzero(pf & nat.MATCH_VALID):
-                    for d in np.flatnonzero(df & nat.MATCH_VALID):
-                        if (pf[p] & ready) == nat.MATCH_VALID and (df[d] & ready) == nat.MATCH_VALID:
-                            continue
-                        if p not in ptext:
-                            ptext[p] = pblock.text_subject(g, int(p), slots, n_alleles, folder)
-                        if d not in dtext:
-                            dtext[d] = block.text_subject(g, int(d), slots, n_alleles, folder)
-                        H, L = folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
-                        stats["host_pairs"] += 1
-                        if H[0] >= min_p0:
-                            host.setdefault(int(p), []).append(((-H[0], -H[1], int(ids[d])), H, L))
-                            stats["candidates"] += 1
-                for p in host:
-                    host[p].sort(key=lambda c: c[0])
-                    del host[p][top_n:]
-            finally:
-                block.close()
+        for block in pairing.donor_blocks():
+            if block.batch is None or not len(pf):
+                pairing.check(block, np.zeros(0, dtype=np.uint8))
+                continue
+            ids = block.lo + block.line_of
+            searcher.run(block.batch, ids.astype(np.uint32))
+            df = searcher.flags()[1]
+            for p, d, H, L in pairing.host_pairs(block, df):
+                stats["host_pairs"] += 1
+                if H[0] >= min_p0:
+                    host.setdefault(int(p), []).append(((-H[0], -H[1], int(ids[d])), H, L))
+                    stats["candidates"] += 1
+            for p in host:
+                host[p].sort(key=lambda c: c[0])
+                del host[p][top_n:]
+            stats["donors_valid"] += int(np.count_nonzero(df & nat.MATCH_VALID))
+            stats["donors_private"] += int(np.count_nonzero(df & nat.MATCH_PRIVATE))
+            stats["kernel_ms"] += searcher.kernel_ms()
+            stats["select_ms"] += searcher.select_ms()
+            stats["blocks"] += 1
         if len(pf):
             dev_hits, dev_n = searcher.results()  # once, after the last block
             stats["download_bytes"] = dev_hits.nbytes + dev_n.nbytes
@@ -222,10 +163,9 @@ def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_l
                     else:
                         hits[line, k]["rec"] = what["rec"]
     finally:
-        if pblock is not None:
-            pblock.close()
+        pairing.close()
         searcher.close()
-    return patient_ok, hits, n_hits, stats
+    return pairing.patient_ok, hits, n_hits, stats
 
 
 def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, graph=None, block_lines=65536):
@@ -241,10 +181,7 @@ def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0
     if graph is None:
         graph = graph_instance(config)
     imp = Imputation(graph, config)
-    with open(patients_path) as fh:
-        plines = fh.read().splitlines()
-    with open(config["imputation_input_file"]) as fh:
-        dlines = fh.read().splitlines()
+    plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
     pok, hits, n_hits, stats = search_donors(imp, plines, dlines, config, keep_loci, top_n, min_p0=min_p0, block_lines=block_lines)
     slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
     nb = 2 * len(slots) + 1

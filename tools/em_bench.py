@@ -30,8 +30,6 @@ def main():
     ap.add_argument("--text-steps", type=int, default=3, help="steps of the text route (tens of seconds each at 100k subjects)")
     args = ap.parse_args()
 
-    import numpy as np
-
     import __graft_entry__ as ge
     ge.build()
     from grim import _native as nat
@@ -61,10 +59,7 @@ def main():
     params = imp._params(dict(cfg, output_haplotypes=True), cfg["planb"], True, True)
     parsed = nat.Parsed(g.adict, ("\n".join(lines) + "\n").encode(), cfg["planb"])
     ps, keep = nat.prior_spec(cfg["priority"], imp.unk_priors, imp.count_by_prob)
-    races = parsed.races()
-    priors = np.ones((max(1, len(races)), P, P))
-    for k, (r1, r2) in enumerate(races):
-        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+    priors = nat.prior_matrices(ps, pops, parsed.races())
     batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
     batch.set_timing(True)
     n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]

@@ -32,8 +32,6 @@ def main():
     ap.add_argument("--text-steps", type=int, default=3, help="steps of the text route (seconds each at 100k subjects)")
     args = ap.parse_args()
 
-    import numpy as np
-
     import __graft_entry__ as ge
     ge.build()
     from grim import _native as nat
@@ -58,7 +56,6 @@ def main():
         os.chdir(cwd)
     imp.on_unsupported = "skip"
     imp.quiet = True
-    P = len(pops)
     keep = [k for k in args.keep.split(",") if k]
     mask = keep_mask(g.locus_slot, keep)
     max_rows = int(cfg["number_of_results"])
@@ -66,10 +63,7 @@ def main():
     params = imp._params(dict(cfg, output_MUUG=True), cfg["planb"], False, False)
     parsed = nat.Parsed(g.adict, ("\n".join(lines) + "\n").encode(), cfg["planb"])
     ps, keep_alive = nat.prior_spec(cfg["priority"], imp.unk_priors, imp.count_by_prob)
-    races = parsed.races()
-    priors = np.ones((max(1, len(races)), P, P))
-    for k, (r1, r2) in enumerate(races):
-        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+    priors = nat.prior_matrices(ps, pops, parsed.races())
     batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
     batch.set_timing(True)
     red = nat.MarginalReducer(ctx, mask, max_rows)

@@ -34,8 +34,6 @@ def main():
     ap.add_argument("--text-donors", type=int, default=1000, help="donors of the text route (scaled to --subjects)")
     args = ap.parse_args()
 
-    import numpy as np
-
     import __graft_entry__ as ge
     ge.build()
     from grim import _native as nat
@@ -61,7 +59,6 @@ def main():
         os.chdir(cwd)
     imp.on_unsupported = "skip"
     imp.quiet = True
-    P = len(pops)
     keep = [k for k in args.keep.split(",") if k]
     counts = [int(x) for x in args.patients.split(",") if x]
     mask = keep_mask(g.locus_slot, keep)
@@ -69,10 +66,7 @@ def main():
     params = imp._params(dict(cfg, output_MUUG=True), cfg["planb"], False, False)
     parsed = nat.Parsed(g.adict, ("\n".join(lines) + "\n").encode(), cfg["planb"])
     ps, keep_alive = nat.prior_spec(cfg["priority"], imp.unk_priors, imp.count_by_prob)
-    races = parsed.races()
-    priors = np.ones((max(1, len(races)), P, P))
-    for k, (r1, r2) in enumerate(races):
-        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+    priors = nat.prior_matrices(ps, pops, parsed.races())
     batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
     batch.set_timing(True)
     matcher = nat.Matcher(ctx, mask, [g.adict.count(s) for s in range(len(g.full_loci))])

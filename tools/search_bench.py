@@ -62,7 +62,6 @@ def main():
         os.chdir(cwd)
     imp.on_unsupported = "skip"
     imp.quiet = True
-    P = len(pops)
     keep = [k for k in args.keep.split(",") if k]
     counts = [int(x) for x in args.patients.split(",") if x]
     tops = [int(x) for x in args.top_n.split(",") if x]
@@ -71,10 +70,7 @@ def main():
     params = imp._params(dict(cfg, output_MUUG=True), cfg["planb"], False, False)
     parsed = nat.Parsed(g.adict, ("\n".join(lines) + "\n").encode(), cfg["planb"])
     ps, keep_alive = nat.prior_spec(cfg["priority"], imp.unk_priors, imp.count_by_prob)
-    races = parsed.races()
-    priors = np.ones((max(1, len(races)), P, P))
-    for k, (r1, r2) in enumerate(races):
-        priors[k] = nat.prior_matrix(ps, pops, r1, r2)
+    priors = nat.prior_matrices(ps, pops, parsed.races())
     n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]
     batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
     matcher = nat.Matcher(ctx, mask, n_alleles)
