@@ -442,6 +442,14 @@ grim_em *grim_em_create(grim_ctx *ctx, const uint32_t n_alleles[GRIM_MAXL], uint
 /* after grim_batch_run, on a batch whose params have em_mr and out_haps and whose graph has n_pops populations (else -3
  * and a grim_last_error text, nothing launched); synchronous; reads the batch's device arrays, copies no result down */
 int grim_em_accumulate(grim_em *em, grim_batch *b);
+/* the same on host records as grim_batch_results / grim_stream_next_records hand them out: res[n_subjects], rows[n_rows] are
+ * uploaded and run through the same kernels in the same order, the subjects' GRIM_T_PMUG row_off / n_rows read against
+ * n_rows (a subject whose rows do not lie inside the rows given is skipped like one without rows).  The call counts as one
+ * batch: spill records carry its ordinal, the statistics add up, grim_em_kernel_ms speaks of it.  -3 and a grim_last_error
+ * text, nothing uploaded, launched or counted, when res is null with n_subjects > 0, rows is null with n_rows > 0, or
+ * n_rows is above 2^31 - 1.  Not defined: a subject whose total is zero, not finite or NaN (the kernels divide by it). */
+int grim_em_accumulate_records(grim_em *em, const grim_subject_result *res, uint32_t n_subjects, const grim_row *rows,
+                               uint64_t n_rows);
 uint64_t grim_em_entries(const grim_em *em); /* (haplotype, population) counters that were added to */
 /* keys / pops / counts [grim_em_entries], in (key, population) order */
 int grim_em_export(grim_em *em, uint64_t *keys, uint32_t *pops, double *counts);

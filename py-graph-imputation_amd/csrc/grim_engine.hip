@@ -1882,6 +1882,7 @@ struct grim_em {
   DevBuf<uint32_t> d_first, d_grp[2], d_idx[2], d_cnt;
   DevBuf<double> d_w, d_ws;
   DevBuf<EmSpill> d_spill;
+  RecordsUpload in;            // the uploaded records of grim_em_accumulate_records
   std::vector<EmSpill> spill;  // every batch's records, in contract order
   uint64_t table_used, entries, n_used, n_planc, n_contrib, n_rehash, last_unsupported;
   uint32_t batch_no;
@@ -1949,15 +1950,15 @@ extern "C" void grim_em_free(grim_em *e) {
 }
 
 // a table twice the size, the entries moved by a kernel with their counters; returns the kernel's milliseconds or < 0
-static double em_rehash(grim_em *e) {
+static double em_rehash(grim_em *e, const std::string &name) {
   grim_ctx *c = e->ctx;
   if (e->cap * 2 * e->T.P > (1ull << 31)) {
-    set_err(c, "grim_em_accumulate: the table cannot grow beyond 2^31 counters");
+    set_err(c, name + ": the table cannot grow beyond 2^31 counters");
     return -1.0;
   }
   EmTable to;
   if (!em_table_alloc(c, to, e->cap * 2, e->T.P)) {
-    set_err(c, "grim_em_accumulate: device allocation failed (rehash)");
+    set_err(c, name + ": device allocation failed (rehash)");
     return -1.0;
   }
   float ms = 0;
@@ -1968,7 +1969,7 @@ static double em_rehash(grim_em *e) {
   if (!ok) {
     (void)hipGetLastError();
     em_table_free(to);
-    set_err(c, "grim_em_accumulate: rehash failed");
+    set_err(c, name + ": rehash failed");
     return -1.0;
   }
   em_table_free(e->T);
@@ -1978,26 +1979,22 @@ static double em_rehash(grim_em *e) {
   return ms;
 }
 
-extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
-  if (!e || !b) return -1;
+// the device sequence on n subjects whose phased rows lie in [0, rows_used) of `rows` (device arrays); one "batch" of batch_no
+static int em_run(grim_em *e, const char *who, const grim_subject_result *res, const grim_row *rows, uint32_t n, uint32_t rows_used) {
   grim_ctx *c = e->ctx;
-  e->last_ms = 0.0;
-  e->last_unsupported = 0;
-  if (!batch_door(c, "grim_em_accumulate", b, 0, e->T.P)) return -3;
-  use_device(c->device);
   hipStream_t st = c->stream;
-  const uint32_t n = b->n_subj;
+  const std::string name(who);
   const uint32_t batch_no = e->batch_no++;
   if (n == 0) return 0;
   if (!e->d_first.reserve((uint64_t)n + 1)) {
-    set_err(c, "grim_em_accumulate: device allocation failed");
+    set_err(c, name + ": device allocation failed");
     return -1;
   }
   // ---- rows per subject -> positions ------------------------------------------------------------------------------
   HIPCHK(hipMemsetAsync(e->d_stat, 0, 8 * 4, st), c, -1);  // the per-call words
   HIPCHK(hipMemsetAsync(e->d_stat + EM_S_FAULT, 0, 8, st), c, -1);
   HIPCHK(hipEventRecord(e->ev[0], st), c, -1);
-  hipLaunchKernelGGL(em_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, b->a.res, n, b->rows_used, e->d_first, e->d_stat);
+  hipLaunchKernelGGL(em_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, e->d_first, e->d_stat);
   hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, e->d_first, n);
   HIPCHK(hipGetLastError(), c, -1);
   HIPCHK(hipEventRecord(e->ev[1], st), c, -1);
@@ -2007,26 +2004,26 @@ extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]), c, -1);
   double total_ms = ms;
-  if (n_rows > b->rows_used || n_rows > 0x3FFFFFFFu) {
-    set_err(c, "grim_em_accumulate: more phased rows than the batch holds");
+  if (n_rows > rows_used || n_rows > 0x3FFFFFFFu) {
+    set_err(c, name + ": more phased rows than the batch holds");
     return -1;
   }
   const uint32_t C = 2 * n_rows;  // contributions
   if (C) {
     // ---- room first: C contributions insert at most C haplotypes -----------------------------------------------------
     while (e->table_used + C > e->cap / 2) {
-      const double r = em_rehash(e);
+      const double r = em_rehash(e, name);
       if (r < 0) return -1;
       total_ms += r;
     }
     const uint32_t n_chunks = (C + GRIM_EM_CHUNK - 1) / GRIM_EM_CHUNK;
     if (!reserve_all(C, C / 4, e->d_grp[0], e->d_grp[1], e->d_idx[0], e->d_idx[1], e->d_w, e->d_ws, e->d_spill) ||
         !e->d_cnt.reserve(256ull * n_chunks + 1)) {
-      set_err(c, "grim_em_accumulate: device allocation failed");
+      set_err(c, name + ": device allocation failed");
       return -1;
     }
     HIPCHK(hipEventRecord(e->ev[2], st), c, -1);
-    hipLaunchKernelGGL(em_weight_kernel, dim3((n + 3) / 4), dim3(256), 0, st, b->a.res, b->a.rows, n, e->d_first, e->T, e->lim, batch_no,
+    hipLaunchKernelGGL(em_weight_kernel, dim3((n + 3) / 4), dim3(256), 0, st, res, rows, n, e->d_first, e->T, e->lim, batch_no,
                        e->d_grp[0], e->d_idx[0], e->d_w, e->d_spill, C, e->d_stat);
     // groups are < cap * P; one bit more sends the records without a group behind them
     uint32_t bits = 1;
@@ -2054,7 +2051,7 @@ extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
   e->last_ms = total_ms;
   e->last_unsupported = h[EM_S_UNSUPPORTED];
   if (h[EM_S_FAULT] || h[EM_S_SPILL] > C) {
-    set_err(c, "grim_em_accumulate: the haplotype table overflowed (internal)");
+    set_err(c, name + ": the haplotype table overflowed (internal)");
     return -1;
   }
   e->table_used = h[EM_S_TABLE];
@@ -2073,6 +2070,28 @@ extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
     });
   }
   return 0;
+}
+
+extern "C" int grim_em_accumulate(grim_em *e, grim_batch *b) {
+  if (!e || !b) return -1;
+  grim_ctx *c = e->ctx;
+  e->last_ms = 0.0;
+  e->last_unsupported = 0;
+  if (!batch_door(c, "grim_em_accumulate", b, 0, e->T.P)) return -3;
+  use_device(c->device);
+  return em_run(e, "grim_em_accumulate", b->a.res, b->a.rows, b->n_subj, b->rows_used);
+}
+
+extern "C" int grim_em_accumulate_records(grim_em *e, const grim_subject_result *res, uint32_t n_subjects, const grim_row *rows,
+                                          uint64_t n_rows) {
+  if (!e) return -1;
+  grim_ctx *c = e->ctx;
+  e->last_ms = 0.0;
+  e->last_unsupported = 0;
+  if (!records_door(c, "grim_em_accumulate_records", (1u << GRIM_MAXL) - 1u, res, n_subjects, rows, n_rows)) return -3;
+  use_device(c->device);
+  if (n_subjects && e->in.upload(c, "grim_em_accumulate_records", res, n_subjects, rows, (uint32_t)n_rows) != 0) return -1;
+  return em_run(e, "grim_em_accumulate_records", e->in.res, e->in.rows, n_subjects, (uint32_t)n_rows);
 }
 
 extern "C" uint64_t grim_em_entries(const grim_em *e) { return e ? e->entries : 0; }

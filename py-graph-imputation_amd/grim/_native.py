@@ -304,8 +304,8 @@ class DeviceBatch(_Handle):
 
 # ---- M-step accumulator (grim_em_*): haplotype / population counts from the phased rows of finished batches ----
 EXPORTS += [
-    "grim_em_create", "grim_em_accumulate", "grim_em_entries", "grim_em_export", "grim_em_spill_count", "grim_em_spill",
-    "grim_em_stats", "grim_em_last_unsupported", "grim_em_kernel_ms", "grim_em_free",
+    "grim_em_create", "grim_em_accumulate", "grim_em_accumulate_records", "grim_em_entries", "grim_em_export", "grim_em_spill_count",
+    "grim_em_spill", "grim_em_stats", "grim_em_last_unsupported", "grim_em_kernel_ms", "grim_em_free",
 ]
 
 SPILL_DT = np.dtype([("key", "<u8"), ("w", "<f8"), ("batch", "<u4"), ("subject", "<u4"), ("row", "<u4"), ("pop", "<u2"), ("side", "<u2")])
@@ -322,6 +322,8 @@ def _em_lib():
         L.grim_em_create.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64]
         L.grim_em_accumulate.restype = C.c_int
         L.grim_em_accumulate.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_em_accumulate_records.restype = C.c_int
+        L.grim_em_accumulate_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64]
         L.grim_em_entries.restype = C.c_uint64
         L.grim_em_entries.argtypes = [C.c_void_p]
         L.grim_em_export.restype = C.c_int
@@ -359,6 +361,11 @@ class EmAccumulator(_Handle):
     def accumulate(self, batch):
         """the counts of one DeviceBatch after its run(); synchronous"""
         self._check(_em_lib().grim_em_accumulate(self.h, batch.h), "grim_em_accumulate")
+
+    def accumulate_records(self, res, rows):
+        """host records (RESULT_DT[n], ROW_DT[m]) through the same kernels; the call counts as one batch"""
+        res, rows, args = _records(res, rows)
+        self._check(_em_lib().grim_em_accumulate_records(self.h, *args), "grim_em_accumulate_records")
 
     def entries(self):
         return int(_em_lib().grim_em_entries(self.h))

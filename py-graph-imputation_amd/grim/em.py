@@ -13,12 +13,15 @@ The reference has no M-step of its own -- its sibling EM package folds the rows 
 Every counter is the left-to-right fp64 sum of its contributions in (line, rank, side) order.
 
 `m_step_counts` runs it on the device, on the rows a batch leaves in HBM (csrc/grim_em.h): no text is formatted, no row
-is copied to the host.  `fold_pmug_text` is the same fold over `.pmug` text in plain Python floats.  The two agree bit for
-bit.  There is no CPU fallback of `m_step_counts`.
+is copied to the host.  `fold_pmug_text` is the same fold over `.pmug` text in plain Python floats, `fold_records` the same
+over record arrays as `EmAccumulator.accumulate_records` takes them.  Device and twins agree bit for bit.  There is no CPU
+fallback of `m_step_counts`.
 """
 
 import gzip
 import os
+
+import numpy as np
 
 from . import _native as nat
 from .blocks import Blocks, note_unsupported, read_lines
@@ -68,6 +71,77 @@ def fold_pmug_text(text):
         rows.append((ha, pa, hb, pb, float(f[3])))
     flush(rows)
     return counts, stats
+
+
+def fold_records(res, rows, n_alleles, n_pops, batch=0, carry=None):
+    """The fold on record arrays (nat.RESULT_DT[n], nat.ROW_DT[m]) as grim_em_accumulate_records defines it (the header
+    comment of csrc/grim_em.h), in plain Python floats -> (keys u64, pops u32, counts f64, spill SPILL_DT, stats).
+
+    A subject is skipped when its status is not OK, it has no phased (T_PMUG) rows, its rows do not lie inside `rows`, or its
+    effective plan (`plan_phased` when non-zero, else `plan`) is `c`; the last is counted in stats["skipped_plan_c"] when the
+    subject is OK and has rows, wherever they point.  total = ((p_0 + p_1) + p_2) ..., w_k = p_k / total (ValueError unless
+    total > 0.0); row k adds w_k to (a_k & keymask, popa_k), then to (b_k & keymask, popb_k), keymask dropping bit 60 and
+    above.  A contribution whose population is `n_pops` or more, or one of whose 12-bit fields is above `n_alleles[slot]`,
+    goes to the spill list instead, in (subject, row, side) order with the fields of grim_em_spill_rec (`batch` as given,
+    `pop` cut to 16 bits as the record holds it).  Entries leave in (key, population) order, as grim_em_export writes them.
+    stats: subjects_used, skipped_plan_c, contributions (spilled ones included) and unsupported (subjects with status
+    UNSUPPORTED), of this call.
+
+    Cuts: fold every cut with one `carry` dict ((key, population) -> count; updated in place) and the call's ordinal as
+    `batch`.  Each call returns the entries of the whole dict so far, and the spill list and stats of that call alone."""
+    n_pops = int(n_pops)
+    limits = [int(x) for x in n_alleles] + [0] * (nat.MAXL - len(n_alleles))
+    keymask = (1 << 60) - 1
+    table = {} if carry is None else carry
+    m = len(rows)
+    res = np.ascontiguousarray(res, dtype=nat.RESULT_DT)
+    rows = np.ascontiguousarray(rows, dtype=nat.ROW_DT)
+    A, B, PR = rows["a"].tolist(), rows["b"].tolist(), rows["prob"].tolist()
+    PA, PB = rows["popa"].tolist(), rows["popb"].tolist()
+    status, plan, plan_phased = res["status"].tolist(), res["plan"].tolist(), res["plan_phased"].tolist()
+    offs, cnts = res["row_off"][:, nat.T_PMUG].tolist(), res["n_rows"][:, nat.T_PMUG].tolist()
+    stats = {"subjects_used": 0, "skipped_plan_c": 0, "contributions": 0, "unsupported": 0}
+    spill = []
+    private = {}  # key -> whether one of its fields is above the dictionary
+    used = []
+    for s in range(len(res)):
+        stats["unsupported"] += status[s] == nat.ST_UNSUPPORTED
+        if status[s] != nat.ST_OK or cnts[s] == 0:
+            continue
+        if (plan_phased[s] or plan[s]) == ord("c"):
+            stats["skipped_plan_c"] += 1
+            continue
+        if offs[s] > m or cnts[s] > m - offs[s]:
+            continue
+        used.append(s)
+    if sum(cnts[s] for s in used) > m:
+        raise ValueError("the subjects' phased rows overlap (more rows than there are)")
+    for s in used:
+        off, n = offs[s], cnts[s]
+        total = PR[off]
+        for k in range(1, n):
+            total = total + PR[off + k]
+        if not total > 0.0:
+            raise ValueError("subject %d: phased rows whose probabilities add up to %r" % (s, total))
+        for k in range(n):
+            w = PR[off + k] / total
+            for side, (key, pop) in enumerate(((A[off + k], PA[off + k]), (B[off + k], PB[off + k]))):
+                key &= keymask
+                priv = private.get(key)
+                if priv is None:
+                    priv = private[key] = any(((key >> (nat.ABITS * q)) & 0xFFF) > limits[q] for q in range(nat.MAXL))
+                if priv or pop >= n_pops:
+                    spill.append((key, w, batch, s, k, pop & 0xFFFF, side))
+                else:
+                    at = (key, pop)
+                    table[at] = table[at] + w if at in table else w
+        stats["subjects_used"] += 1
+        stats["contributions"] += 2 * n
+    order = sorted(table)
+    keys = np.array([k for k, _ in order], dtype=np.uint64)
+    pops = np.array([p for _, p in order], dtype=np.uint32)
+    counts = np.array([table[at] for at in order], dtype=np.float64)
+    return keys, pops, counts, np.array(spill, dtype=nat.SPILL_DT), stats
 
 
 def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
