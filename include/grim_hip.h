@@ -463,6 +463,50 @@ uint64_t grim_em_last_unsupported(const grim_em *em);
 double grim_em_kernel_ms(const grim_em *em);
 void grim_em_free(grim_em *em);
 
+/* ======================= EM on a fixed support: the graph's frequencies from M-step counts (csrc/grim_refresh.h) =======
+ * The reference has no counterpart: after an M-step it writes POP.freqs.gz, regenerates the graph files and loads them again
+ * (grim/em.py em_iteration does the same here).  When the support is kept only the numbers in freq change, so the refresh
+ * recomputes them where they lie.  The operation, every sum's order included (csrc/grim_refresh.h has the full text):
+ *   full nodes f_0 < ... < f_{F-1}: the nodes with node_mask == full_mask, in node-id order;
+ *   c[i][p] = the count of (node_key[f_i] with bit GRIM_KEY_GRAPH_ORDER and above dropped, p) when the counts hold that entry,
+ *     else +0.0; counts of haplotypes that are not full nodes of the graph take no part;
+ *   s_b[p] = ((+0.0 + c[bB][p]) + c[bB+1][p]) + ... over block b of B = GRIM_REFRESH_BLOCK positions,
+ *   T_p = ((+0.0 + s_0[p]) + s_1[p]) + ... over the blocks in order (fp64, no fma);
+ *   new[f_i][p] = c[i][p] / T_p; for a partial node v, new[v][p] = ((+0.0 + new[r_0][p]) + new[r_1][p]) + ... over its top-link
+ *     row a_nbr[a_start[v] .. e(v)) in stored order, e(v) = a_start[v + 1] for v < n_nodes - 1 and n_a_nbr for the last node;
+ *   the full-haplotype table's inline frequency of a key becomes new[n][0], n the highest-numbered full node of that key.
+ * A graph can be refreshed when, in the descriptor grim_graph_upload was given, the rows of the partial nodes in node order
+ * tile a_nbr[0 .. n_a_nbr) without gap or overlap, every row is non-empty, every entry is a full node and every entry's key cut
+ * to the slots of node_mask[v] equals node_key[v] (every graph grim_graphgen_csv makes).  grim_graph_upload decides that and
+ * keeps the answer; what it returns and uploads does not change.
+ * Refusals answer -3 with a grim_last_error text, launch nothing that writes and leave every bit of the graph's frequencies as
+ * it was: the graph is not refreshable; the accumulator belongs to another context or has another number of populations;
+ * records door: a null array with n > 0, pops[i] >= n_pops, a key with a bit at or above GRIM_KEY_GRAPH_ORDER, entries not
+ * strictly ascending in (key, pop), a count that is negative, NaN or infinite; some T_p is not finite or not > 0.0 (a
+ * population without any count inside the support; `stats` then holds the totals and n_full, everything else 0).
+ * The new values are computed into a shadow buffer and committed in place, at the same device addresses, after the totals were
+ * read.  The caller guarantees that no batch or stream of this graph is in flight; the call synchronises the context's stream
+ * before its first launch and before it returns.  No floor, no pseudo-count, no new haplotypes, one device's counts. */
+#define GRIM_REFRESH_BLOCK 4096 /* positions of one block of the totals' two-level fold */
+typedef struct {
+  double total[GRIM_MAXPOP]; /* T_p */
+  double delta;              /* the largest |new - old| over the full nodes and populations */
+  uint64_t matched;          /* (full node, population) pairs with an entry in the counts */
+  uint64_t zero_full;        /* full nodes whose new vector is all zero */
+  uint64_t n_full;           /* F */
+} grim_refresh_stats;
+/* the counts of an accumulator, where its table lies; stats may be NULL */
+int grim_graph_refresh(grim_graph *g, grim_em *em, grim_refresh_stats *stats);
+/* the counts as host arrays keys / pops / counts [n] in grim_em_export's order */
+int grim_graph_refresh_records(grim_graph *g, const uint64_t *keys, const uint32_t *pops, const double *counts, uint64_t n,
+                               grim_refresh_stats *stats);
+/* out[n_nodes][n_pops]: the frequencies as they lie on the device */
+int grim_graph_freq(grim_graph *g, double *out);
+/* device time of the last refresh that launched: its kernels and the commit between their own start/stop events */
+double grim_graph_refresh_ms(const grim_graph *g);
+/* 1 when grim_graph_upload found the graph refreshable, else 0 */
+int grim_graph_refreshable(const grim_graph *g);
+
 /* ======================= marginal genotype tables on a subset of the loci (csrc/grim_marginal.h) ======================
  * What scripts/reduce_loci.py does to a printed .umug file -- drop a locus from every genotype, add the probabilities of
  * genotypes that became equal, sort again, keep the top rows -- on the genotype rows a finished batch holds in HBM, for any

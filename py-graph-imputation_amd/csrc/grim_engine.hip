@@ -22,6 +22,7 @@
 #include "grim_tables.h"
 #include "grim_tokdev.h"
 #include "grim_em.h"
+#include "grim_refresh.h"
 #include "grim_marginal.h"
 #include "grim_match.h"
 #include "grim_search.h"
@@ -290,12 +291,22 @@ struct grim_ctx {
   std::vector<grim_batch *> spare;
 };
 
+struct RefreshState;  // device buffers of grim_graph_refresh, made by the first refresh (below the M-step accumulator)
+
 struct grim_graph {
   grim_ctx *ctx;
   DevGraph d;
   std::vector<void *> bufs;
   uint64_t bytes;
   uint32_t max_label;
+  // grim_graph_refresh (grim_refresh.h): whether the descriptor's top-link rows can be trusted for it, and why not; the partial
+  // nodes by row length (host copies: they go to the device with the first refresh)
+  bool refreshable = false;
+  std::string refresh_why;
+  uint32_t n_a_nbr = 0, full_first = 0, n_full = 0;
+  std::vector<uint32_t> rf_short, rf_long;
+  RefreshState *rf = nullptr;
+  double refresh_ms = 0.0;
 };
 
 // Timing mode: one entry per timed interval of a run.  Each has a start/stop event pair in its batch, and a row below with
@@ -537,6 +548,64 @@ static uint64_t host_mix64(uint64_t x) {
   return x;
 }
 
+// Whether grim_graph_refresh may trust the descriptor's top-link rows (the conditions: grim_refresh.h), kept on the graph as a
+// flag plus a reason text; the partial nodes go to the short-row or the long-row list on the way.  Reads the host arrays only.
+static void refresh_check_rows(grim_graph *g, const grim_graph_desc *d) {
+  const uint32_t V = d->n_nodes;
+  auto no = [&](const std::string &why) {
+    g->refreshable = false;
+    g->refresh_why = why;
+    g->rf_short.clear();
+    g->rf_long.clear();
+  };
+  if (d->full_mask >= (1u << GRIM_MAXL)) return no("full_mask names a locus slot beyond GRIM_MAXL");
+  if (d->n_a_nbr > 0xFFFFFFFFull) return no("more than 2^32 - 1 top links");
+  const uint32_t n_a = (uint32_t)d->n_a_nbr;
+  const uint32_t f_lo = d->lab_start[d->full_mask], f_hi = d->lab_start[d->full_mask + 1];
+  if (f_lo > f_hi || f_hi > V) return no("lab_start does not lie inside the nodes");
+  {  // the full nodes of lab_nodes are the full nodes, in node-id order
+    uint32_t at = f_lo;
+    for (uint32_t v = 0; v < V; ++v)
+      if (d->node_mask[v] == d->full_mask) {
+        if (at >= f_hi || d->lab_nodes[at] != v) return no("lab_nodes does not list the full nodes in node order");
+        ++at;
+      }
+    if (at != f_hi) return no("lab_nodes does not list the full nodes in node order");
+  }
+  uint64_t slots[1u << GRIM_MAXL];  // the key fields of a label mask
+  for (uint32_t m = 0; m < (1u << GRIM_MAXL); ++m) {
+    slots[m] = 0;
+    for (uint32_t q = 0; q < GRIM_MAXL; ++q)
+      if ((m >> q) & 1u) slots[m] |= 0xFFFull << (GRIM_ABITS * q);
+  }
+  g->rf_short.clear();
+  g->rf_long.clear();
+  uint32_t pos = 0;
+  for (uint32_t v = 0; v < V; ++v) {
+    const uint32_t m = d->node_mask[v];
+    if (m == d->full_mask) continue;
+    const std::string node = "partial node " + std::to_string(v);
+    if (m >= (1u << GRIM_MAXL)) return no(node + ": label mask beyond GRIM_MAXL");
+    const uint32_t lo = d->a_start[v], hi = v + 1 < V ? d->a_start[v + 1] : n_a;
+    if (lo != pos) return no(node + ": its top-link row does not begin where the row before it ends");
+    if (hi <= lo) return no(node + ": empty top-link row");
+    if (hi > n_a) return no(node + ": its top-link row ends beyond the links");
+    for (uint32_t e = lo; e < hi; ++e) {
+      const uint32_t r = d->a_nbr[e];
+      if (r >= V || d->node_mask[r] != d->full_mask) return no(node + ": a top link that does not end at a full node");
+      if ((d->node_key[r] & slots[m]) != d->node_key[v]) return no(node + ": a top link to a full haplotype that does not project onto it");
+    }
+    (hi - lo <= RF_SHORT_MAX ? g->rf_short : g->rf_long).push_back(v);
+    pos = hi;
+  }
+  if (pos != n_a) return no("top links beyond the rows of the partial nodes");
+  g->refreshable = true;
+  g->refresh_why.clear();
+  g->n_a_nbr = n_a;
+  g->full_first = f_lo;
+  g->n_full = f_hi - f_lo;
+}
+
 extern "C" grim_graph *grim_graph_upload(grim_ctx *c, const grim_graph_desc *d) {
   if (!c || !d) return nullptr;
   hipSetDevice(c->device);
@@ -634,12 +703,16 @@ extern "C" grim_graph *grim_graph_upload(grim_ctx *c, const grim_graph_desc *d) 
     delete g;
     return nullptr;
   }
+  refresh_check_rows(g, d);
   return g;
 }
+
+static void refresh_state_free(RefreshState *rf);
 
 extern "C" void grim_graph_free(grim_graph *g) {
   if (!g) return;
   hipSetDevice(g->ctx->device);
+  refresh_state_free(g->rf);
   for (void *p : g->bufs) hipFree(p);
   delete g;
 }
@@ -2150,6 +2223,178 @@ extern "C" int grim_em_export(grim_em *e, uint64_t *keys, uint32_t *pops, double
   }
   return 0;
 }
+
+// =================================================================================================
+// EM on a fixed support (grim_refresh.h): the graph's frequencies from M-step counts
+// =================================================================================================
+struct RefreshState {
+  DevBuf<uint32_t> d_short, d_long;  // the partial nodes by row length
+  DevBuf<double> d_c, d_bsum, d_total, d_shadow;
+  DevBuf<unsigned long long> d_stat;
+  DevBuf<unsigned long long> d_keys;  // the uploaded records of grim_graph_refresh_records
+  DevBuf<uint32_t> d_pops;
+  DevBuf<double> d_counts;
+  Events<4> ev;
+};
+
+static void refresh_state_free(RefreshState *rf) { delete rf; }
+
+// the graph's refresh state, made by the first refresh of a refreshable graph: every buffer whose size the graph fixes, and
+// the two node lists on the device; null and a text on failure
+static RefreshState *refresh_state(grim_graph *g, const char *who) {
+  if (g->rf) return g->rf;
+  const uint32_t V = g->d.n_nodes, P = g->d.P, F = g->n_full;
+  const uint32_t n_short = (uint32_t)g->rf_short.size(), n_long = (uint32_t)g->rf_long.size();
+  const uint32_t n_blocks = (F + GRIM_REFRESH_BLOCK - 1) / GRIM_REFRESH_BLOCK;
+  RefreshState *rf = new RefreshState();
+  bool ok = rf->ev.create() && rf->d_short.reserve((uint64_t)n_short + 1) && rf->d_long.reserve((uint64_t)n_long + 1) &&
+            rf->d_c.reserve((uint64_t)F * P + 1) && rf->d_bsum.reserve((uint64_t)n_blocks * P + 1) && rf->d_total.reserve(GRIM_MAXPOP) &&
+            rf->d_shadow.reserve((uint64_t)V * P + 1) && rf->d_stat.reserve(RF_S_COUNT);
+  ok = ok && (!n_short || hipMemcpy(rf->d_short, g->rf_short.data(), 4ull * n_short, hipMemcpyHostToDevice) == hipSuccess) &&
+       (!n_long || hipMemcpy(rf->d_long, g->rf_long.data(), 4ull * n_long, hipMemcpyHostToDevice) == hipSuccess);
+  if (!ok) {
+    (void)hipGetLastError();
+    delete rf;
+    set_err(g->ctx, std::string(who) + ": device allocation failed");
+    return nullptr;
+  }
+  return g->rf = rf;
+}
+
+// the device sequence behind both doors; C.T or C.keys / pops / counts are device arrays
+static int refresh_run(grim_graph *g, const char *who, RfCounts C, grim_refresh_stats *stats) {
+  grim_ctx *c = g->ctx;
+  hipStream_t st = c->stream;
+  const std::string name(who);
+  const DevGraph &D = g->d;
+  const uint32_t V = D.n_nodes, P = D.P, F = g->n_full;
+  const uint32_t n_short = (uint32_t)g->rf_short.size(), n_long = (uint32_t)g->rf_long.size();
+  const uint32_t n_blocks = (F + GRIM_REFRESH_BLOCK - 1) / GRIM_REFRESH_BLOCK;
+  grim_refresh_stats out;
+  memset(&out, 0, sizeof(out));
+  out.n_full = F;
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  if (!refresh_state(g, who)) return -1;
+  RefreshState &R = *g->rf;
+  const uint32_t *full = D.lab_nodes + g->full_first;
+  const size_t lds = sizeof(double) * RF_CHUNK * P + sizeof(uint32_t) * RF_CHUNK;
+  // ---- everything into the shadow ---------------------------------------------------------------------------------------
+  HIPCHK(hipMemsetAsync(R.d_stat, 0, 8 * RF_S_COUNT, st), c, -1);
+  HIPCHK(hipMemsetAsync(R.d_total, 0, 8 * GRIM_MAXPOP, st), c, -1);
+  HIPCHK(hipEventRecord(R.ev[0], st), c, -1);
+  if (F) {
+    const uint32_t n_fp = (uint32_t)(((uint64_t)F * P + 255) / 256);
+    hipLaunchKernelGGL(rf_lookup_kernel, dim3(n_fp), dim3(256), 0, st, full, F, V, P, D.node_key, C, R.d_c, R.d_stat);
+    hipLaunchKernelGGL(rf_blocksum_kernel, dim3(n_blocks), dim3(64), lds, st, R.d_c, F, P, R.d_bsum);
+    hipLaunchKernelGGL(rf_total_kernel, dim3(1), dim3(64), 0, st, R.d_bsum, n_blocks, P, R.d_total);
+    hipLaunchKernelGGL(rf_divide_kernel, dim3((F + 255) / 256), dim3(256), 0, st, full, F, V, P, R.d_c, R.d_total, D.freq, R.d_shadow,
+                       R.d_stat);
+    if (n_short)
+      hipLaunchKernelGGL(rf_short_kernel, dim3((uint32_t)(((uint64_t)n_short * P + 255) / 256)), dim3(256), 0, st, R.d_short, n_short, V, P,
+                         D.a_start, D.a_nbr, g->n_a_nbr, R.d_shadow, R.d_stat);
+    if (n_long)
+      hipLaunchKernelGGL(rf_long_kernel, dim3(n_long), dim3(64), lds, st, R.d_long, n_long, V, P, D.a_start, D.a_nbr, g->n_a_nbr,
+                         R.d_shadow, R.d_stat);
+    HIPCHK(hipGetLastError(), c, -1);
+  }
+  HIPCHK(hipEventRecord(R.ev[1], st), c, -1);
+  HIPCHK(hipMemcpyAsync(out.total, R.d_total, 8 * P, hipMemcpyDeviceToHost, st), c, -1);
+  uint64_t h[RF_S_COUNT];
+  if (read_stat<RF_S_COUNT, 1>(c, R.d_stat, h) != 0) return -1;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, R.ev[0], R.ev[1]), c, -1);
+  g->refresh_ms = ms;
+  if (h[RF_S_FAULT]) {
+    set_err(c, name + ": a top-link row or the full-node list does not lie inside the graph (internal)");
+    return -1;
+  }
+  for (uint32_t p = 0; p < P; ++p)
+    if (!(out.total[p] > 0.0 && out.total[p] <= 1.7976931348623157e308)) {  // finite and > 0 (false for a NaN)
+      if (stats) *stats = out;
+      set_err(c, name + ": population " + std::to_string(p) + " has no count inside the support (its total is not finite or not > 0)");
+      return -3;
+    }
+  // ---- commit: in place, at the addresses every batch and stream of the graph holds ---------------------------------------
+  HIPCHK(hipEventRecord(R.ev[2], st), c, -1);
+  HIPCHK(hipMemcpyAsync(const_cast<double *>(D.freq), R.d_shadow, 8ull * V * P, hipMemcpyDeviceToDevice, st), c, -1);
+  hipLaunchKernelGGL(rf_fht_kernel, dim3((F + 255) / 256), dim3(256), 0, st, full, F, V, P, D.node_key, D.ht, D.ht_mask,
+                     const_cast<FullEnt *>(D.fht), D.fht_mask, D.freq);
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(R.ev[3], st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  HIPCHK(hipEventElapsedTime(&ms, R.ev[2], R.ev[3]), c, -1);
+  g->refresh_ms += ms;
+  out.matched = h[RF_S_MATCHED];
+  out.zero_full = h[RF_S_ZERO_FULL];
+  memcpy(&out.delta, &h[RF_S_DELTA], 8);
+  if (stats) *stats = out;
+  return 0;
+}
+
+extern "C" int grim_graph_refresh(grim_graph *g, grim_em *e, grim_refresh_stats *stats) {
+  if (!g || !e) return -1;
+  grim_ctx *c = g->ctx;
+  const char *who = "grim_graph_refresh";
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (!g->refreshable) return refuse(c, who, ("the graph is not refreshable: " + g->refresh_why).c_str()), -3;
+  if (e->ctx != c) return refuse(c, who, "the accumulator belongs to another context"), -3;
+  if (e->T.P != g->d.P) return refuse(c, who, "the accumulator has another number of populations"), -3;
+  use_device(c->device);
+  RfCounts C;
+  memset(&C, 0, sizeof(C));
+  C.T = e->T;
+  return refresh_run(g, who, C, stats);
+}
+
+extern "C" int grim_graph_refresh_records(grim_graph *g, const uint64_t *keys, const uint32_t *pops, const double *counts, uint64_t n,
+                                          grim_refresh_stats *stats) {
+  if (!g) return -1;
+  grim_ctx *c = g->ctx;
+  const char *who = "grim_graph_refresh_records";
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (!g->refreshable) return refuse(c, who, ("the graph is not refreshable: " + g->refresh_why).c_str()), -3;
+  if (n && (!keys || !pops || !counts)) return refuse(c, who, "a null array with n > 0"), -3;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (pops[i] >= g->d.P) return refuse(c, who, "a population at or above the graph's number of populations"), -3;
+    if (keys[i] >> GRIM_KEY_GRAPH_ORDER) return refuse(c, who, "a key with a bit at or above GRIM_KEY_GRAPH_ORDER"), -3;
+    if (i && !(keys[i - 1] < keys[i] || (keys[i - 1] == keys[i] && pops[i - 1] < pops[i])))
+      return refuse(c, who, "the entries are not strictly ascending in (key, pop)"), -3;
+    if (!(counts[i] >= 0.0 && counts[i] <= 1.7976931348623157e308)) return refuse(c, who, "a count that is negative, NaN or infinite"), -3;
+  }
+  use_device(c->device);
+  if (!refresh_state(g, who)) return -1;
+  RefreshState &R = *g->rf;
+  if (!R.d_keys.reserve(n + 1) || !R.d_pops.reserve(n + 1) || !R.d_counts.reserve(n + 1)) {
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
+  }
+  if (n) {
+    HIPCHK(hipMemcpyAsync(R.d_keys, keys, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+    HIPCHK(hipMemcpyAsync(R.d_pops, pops, 4 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+    HIPCHK(hipMemcpyAsync(R.d_counts, counts, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+    HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+  }
+  RfCounts C;
+  memset(&C, 0, sizeof(C));
+  C.records = 1;
+  C.keys = R.d_keys;
+  C.pops = R.d_pops;
+  C.counts = R.d_counts;
+  C.n = n;
+  return refresh_run(g, who, C, stats);
+}
+
+extern "C" int grim_graph_freq(grim_graph *g, double *out) {
+  if (!g || !out) return -1;
+  grim_ctx *c = g->ctx;
+  use_device(c->device);
+  HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+  HIPCHK(hipMemcpy(out, g->d.freq, 8ull * g->d.n_nodes * g->d.P, hipMemcpyDeviceToHost), c, -1);
+  return 0;
+}
+
+extern "C" double grim_graph_refresh_ms(const grim_graph *g) { return g ? g->refresh_ms : 0.0; }
+extern "C" int grim_graph_refreshable(const grim_graph *g) { return g && g->refreshable ? 1 : 0; }
 
 // =================================================================================================
 // Marginal genotype tables (grim_marginal.h): the UMUG rows of a finished batch reduced to a subset of the loci

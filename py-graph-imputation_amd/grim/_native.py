@@ -249,6 +249,75 @@ class DeviceGraph(_Handle):
     def device_bytes(self):
         return int(lib().grim_graph_device_bytes(self.h))
 
+    # ---- EM on a fixed support (grim_graph_refresh*, include/grim_hip.h): the frequencies from M-step counts ----
+    def refreshable(self):
+        return bool(_refresh_lib().grim_graph_refreshable(self.h))
+
+    def _refreshed(self, rc, name, st):
+        self._check(rc, name)
+        P = int(self._keep["n_pops"])
+        return {"total": [float(x) for x in st.total[:P]], "delta": float(st.delta), "matched": int(st.matched),
+                "zero_full": int(st.zero_full), "n_full": int(st.n_full), "kernel_ms": self.refresh_ms()}
+
+    def refresh(self, acc):
+        """new frequencies from the counts of an EmAccumulator, where its table lies -> the statistics (a dict); synchronous.
+        The caller guarantees that no batch or stream of this graph is in flight."""
+        st = RefreshStats()
+        return self._refreshed(_refresh_lib().grim_graph_refresh(self.h, acc.h, C.byref(st)), "grim_graph_refresh", st)
+
+    def refresh_records(self, keys, pops, counts):
+        """the same from host arrays keys u64 / pops u32 / counts f64 in EmAccumulator.export's order"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        pops = np.ascontiguousarray(pops, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.float64)
+        if not (keys.ndim == 1 and keys.shape == pops.shape == counts.shape):
+            raise ValueError("keys, pops and counts must be one-dimensional and of one length")
+        n = keys.shape[0]
+        st = RefreshStats()
+        rc = _refresh_lib().grim_graph_refresh_records(self.h, _ptr(keys) if n else None, _ptr(pops) if n else None,
+                                                       _ptr(counts) if n else None, n, C.byref(st))
+        return self._refreshed(rc, "grim_graph_refresh_records", st)
+
+    def freq(self):
+        """the frequencies as they lie on the device -> f64 [n_nodes][n_pops]"""
+        out = np.zeros((int(self._keep["n_nodes"]), int(self._keep["n_pops"])), dtype=np.float64)
+        self._check(_refresh_lib().grim_graph_freq(self.h, _ptr(out)), "grim_graph_freq")
+        return out
+
+    def refresh_ms(self):
+        return float(_refresh_lib().grim_graph_refresh_ms(self.h))
+
+
+EXPORTS += ["grim_graph_refresh", "grim_graph_refresh_records", "grim_graph_freq", "grim_graph_refresh_ms", "grim_graph_refreshable"]
+
+REFRESH_BLOCK = 4096
+
+
+class RefreshStats(C.Structure):
+    _fields_ = [("total", C.c_double * MAXPOP), ("delta", C.c_double), ("matched", C.c_uint64), ("zero_full", C.c_uint64),
+                ("n_full", C.c_uint64)]
+
+
+_refresh_ready = False
+
+
+def _refresh_lib():
+    global _refresh_ready
+    L = lib()
+    if not _refresh_ready:
+        L.grim_graph_refresh.restype = C.c_int
+        L.grim_graph_refresh.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RefreshStats)]
+        L.grim_graph_refresh_records.restype = C.c_int
+        L.grim_graph_refresh_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RefreshStats)]
+        L.grim_graph_freq.restype = C.c_int
+        L.grim_graph_freq.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_graph_refresh_ms.restype = C.c_double
+        L.grim_graph_refresh_ms.argtypes = [C.c_void_p]
+        L.grim_graph_refreshable.restype = C.c_int
+        L.grim_graph_refreshable.argtypes = [C.c_void_p]
+        _refresh_ready = True
+    return L
+
 
 class DeviceBatch(_Handle):
     """Subjects resident in HBM + result/scratch buffers (grim_batch)."""

@@ -144,22 +144,14 @@ def fold_records(res, rows, n_alleles, n_pops, batch=0, carry=None):
     return keys, pops, counts, np.array(spill, dtype=nat.SPILL_DT), stats
 
 
-def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
-    """The M-step on the device.  `lines_or_path`: input lines (a list) or the path of an input file; `config`: the
-    configuration dict of `load_config`.  The input is cut into blocks of `block_lines` lines; each is tokenised, imputed
-    as one device batch (em_mr on, phased output on, `em` as impute_file's) and its rows are added to the accumulator
-    where they lie.  `output_MUUG` stays as the configuration has it: the reference's phased pass starts from what the MUUG
-    pass left when that one ended in Plan C (impute.py:1637-1654), so the phased rows of some subjects differ with it off,
-    and the counts are those of the rows the configured run prints.  -> ({pop: {haplotype: count}}, stats); the cuts do not show in any bit of a count.
-    Subjects the device cannot answer follow `imputation.on_unsupported` as in `impute_lines_block`."""
-    lines = read_lines(lines_or_path)
-    g = imputation.netGraph
-    pops = imputation.populations
-    shared = Blocks(imputation, config, planb, True, em, output_haplotypes=True)
-    n_slots = len(g.full_loci)
-    acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(pops), first_capacity)
+def _accumulate_blocks(imputation, shared, lines, block_lines, acc):
+    """The block loop of the M-step: `lines` in blocks of `block_lines`, each tokenised, imputed as one device batch of
+    `shared` (a Blocks) and added to the accumulator `acc` where its rows lie.  -> (spilled, kernel_ms, blocks); spilled:
+    (pop index, haplotype text) -> count, the haplotypes that hold an allele the dictionary does not know.  Resets and fills
+    imputation.unsupported."""
+    n_slots = len(imputation.netGraph.full_loci)
     imputation.unsupported = []
-    spilled = {}  # (pop index, haplotype text) -> count: haplotypes that hold an allele the dictionary does not know
+    spilled = {}
     kernel_ms = 0.0
     n_blocks = 0
     cut = shared.cut(lines, max(1, int(block_lines)))
@@ -180,6 +172,27 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
                     at = (int(rec["pop"]), name)
                     spilled[at] = spilled[at] + float(rec["w"]) if at in spilled else float(rec["w"])
             note_unsupported(imputation, bad)
+    finally:
+        cut.close()
+    return spilled, kernel_ms, n_blocks
+
+
+def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
+    """The M-step on the device.  `lines_or_path`: input lines (a list) or the path of an input file; `config`: the
+    configuration dict of `load_config`.  The input is cut into blocks of `block_lines` lines; each is tokenised, imputed
+    as one device batch (em_mr on, phased output on, `em` as impute_file's) and its rows are added to the accumulator
+    where they lie.  `output_MUUG` stays as the configuration has it: the reference's phased pass starts from what the MUUG
+    pass left when that one ended in Plan C (impute.py:1637-1654), so the phased rows of some subjects differ with it off,
+    and the counts are those of the rows the configured run prints.  -> ({pop: {haplotype: count}}, stats); the cuts do not show in any bit of a count.
+    Subjects the device cannot answer follow `imputation.on_unsupported` as in `impute_lines_block`."""
+    lines = read_lines(lines_or_path)
+    g = imputation.netGraph
+    pops = imputation.populations
+    shared = Blocks(imputation, config, planb, True, em, output_haplotypes=True)
+    n_slots = len(g.full_loci)
+    acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(pops), first_capacity)
+    try:
+        spilled, kernel_ms, n_blocks = _accumulate_blocks(imputation, shared, lines, block_lines, acc)
         keys, kpops, vals = acc.export()
         counts = {}
         names = {}
@@ -193,7 +206,6 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
         stats = acc.stats()
         stats.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
     finally:
-        cut.close()
         acc.close()
     return counts, stats
 
@@ -241,3 +253,158 @@ def em_iteration(conf_file, graph=None, block_lines=65536):
     produce_hpf(conf_file, quiet=True)
     graph_freqs(conf_file, for_em=True, em_pop=config["pops"])
     return graph_instance(config), counts
+
+
+# ---- EM on a fixed support: the graph's frequencies from M-step counts (csrc/grim_refresh.h) ----------------
+KEYMASK = (1 << 60) - 1  # GRIM_EM_KEYMASK: the alleles of a key
+
+
+def refreshable_rows(arrays):
+    """Whether the top-link rows of a graph's arrays can be trusted for a refresh, decided as grim_graph_upload decides it:
+    the rows of the partial nodes, in node order, row of v = a_nbr[a_start[v] .. e(v)) with e(v) = a_start[v + 1] for
+    v < V - 1 and e(V - 1) = len(a_nbr) (a_start[V] is the reference's sentinel quirk, not an end), tile a_nbr without gap
+    or overlap; every row is non-empty; every entry is a full node whose key, cut to the slots of node_mask[v], is
+    node_key[v].  -> (full node ids in node order, {partial node: (lo, hi)}) or raises ValueError with the reason."""
+    V, full_mask = int(arrays["n_nodes"]), int(arrays["full_mask"])
+    keys, masks = arrays["node_key"].tolist(), arrays["node_mask"].tolist()
+    a_start, a_nbr = arrays["a_start"].tolist(), arrays["a_nbr"].tolist()
+    lab_start, lab_nodes = arrays["lab_start"].tolist(), arrays["lab_nodes"].tolist()
+    n_a = len(a_nbr)
+    if full_mask >= 1 << nat.MAXL:
+        raise ValueError("not refreshable: full_mask names a locus slot beyond MAXL")
+    full = [v for v in range(V) if masks[v] == full_mask]
+    f_lo, f_hi = lab_start[full_mask], lab_start[full_mask + 1]
+    if f_lo > f_hi or f_hi > V or lab_nodes[f_lo:f_hi] != full:
+        raise ValueError("not refreshable: lab_nodes does not list the full nodes in node order")
+    slots = [sum(0xFFF << (nat.ABITS * q) for q in range(nat.MAXL) if (m >> q) & 1) for m in range(1 << nat.MAXL)]
+    rows = {}
+    pos = 0
+    for v in range(V):
+        m = masks[v]
+        if m == full_mask:
+            continue
+        if m >= 1 << nat.MAXL:
+            raise ValueError("not refreshable: partial node %d: label mask beyond MAXL" % v)
+        lo, hi = a_start[v], a_start[v + 1] if v + 1 < V else n_a
+        if lo != pos:
+            raise ValueError("not refreshable: partial node %d: its top-link row does not begin where the row before it ends" % v)
+        if hi <= lo:
+            raise ValueError("not refreshable: partial node %d: empty top-link row" % v)
+        if hi > n_a:
+            raise ValueError("not refreshable: partial node %d: its top-link row ends beyond the links" % v)
+        for e in range(lo, hi):
+            r = a_nbr[e]
+            if r >= V or masks[r] != full_mask:
+                raise ValueError("not refreshable: partial node %d: a top link that does not end at a full node" % v)
+            if keys[r] & slots[m] != keys[v]:
+                raise ValueError("not refreshable: partial node %d: a top link to a full haplotype that does not project onto it" % v)
+        rows[v] = (lo, hi)
+        pos = hi
+    if pos != n_a:
+        raise ValueError("not refreshable: top links beyond the rows of the partial nodes")
+    return full, rows
+
+
+def refresh_freq_arrays(arrays, keys, pops, counts):
+    """The CPU twin of grim_graph_refresh_records in plain Python floats, every sum in the contract's order (the header
+    comment of csrc/grim_refresh.h): `arrays` as Graph.arrays holds them, keys / pops / counts [n] in EmAccumulator.export's
+    order -> (freq f64 [n_nodes][n_pops], stats with total, delta, matched, zero_full, n_full).  The refusals of the device
+    call are raised as ValueError; `arrays` is not changed."""
+    V, P = int(arrays["n_nodes"]), int(arrays["n_pops"])
+    full, rows = refreshable_rows(arrays)
+    if keys is None or pops is None or counts is None:
+        raise ValueError("a null array")
+    K = np.asarray(keys).tolist()
+    Q = np.asarray(pops).tolist()
+    Cn = [float(x) for x in np.asarray(counts).tolist()]
+    if not len(K) == len(Q) == len(Cn):
+        raise ValueError("keys, pops and counts of different lengths")
+    table = {}
+    for i in range(len(K)):
+        k, q, c = int(K[i]), int(Q[i]), Cn[i]
+        if q < 0 or q >= P:
+            raise ValueError("a population at or above the graph's number of populations")
+        if k < 0 or k >> 60:
+            raise ValueError("a key with a bit at or above bit 60")
+        if i and not (int(K[i - 1]), int(Q[i - 1])) < (k, q):
+            raise ValueError("the entries are not strictly ascending in (key, pop)")
+        if not (c >= 0.0 and c != float("inf")):
+            raise ValueError("a count that is negative, NaN or infinite")
+        table[(k, q)] = c
+    node_key = arrays["node_key"].tolist()
+    old = arrays["freq"]
+    F = len(full)
+    matched = 0
+    c = []
+    for v in full:
+        vec = []
+        for p in range(P):
+            x = table.get((node_key[v] & KEYMASK, p))
+            matched += x is not None
+            vec.append(0.0 if x is None else x)
+        c.append(vec)
+    B = nat.REFRESH_BLOCK
+    total = []
+    for p in range(P):
+        t = 0.0
+        for b in range(0, F, B):
+            s = 0.0
+            for i in range(b, min(b + B, F)):
+                s = s + c[i][p]
+            t = t + s
+        total.append(t)
+    for p in range(P):
+        if not (total[p] > 0.0 and total[p] != float("inf")):
+            raise ValueError("population %d has no count inside the support (its total is %r)" % (p, total[p]))
+    new = [None] * V
+    delta = 0.0
+    zero_full = 0
+    for i, v in enumerate(full):
+        vec = [c[i][p] / total[p] for p in range(P)]
+        new[v] = vec
+        oldv = old[v].tolist()
+        for p in range(P):
+            d = abs(vec[p] - oldv[p])
+            if d > delta:
+                delta = d
+        zero_full += all(x == 0.0 for x in vec)
+    a_nbr = arrays["a_nbr"].tolist()
+    for v, (lo, hi) in rows.items():
+        vec = [0.0] * P
+        for e in range(lo, hi):
+            src = new[a_nbr[e]]
+            for p in range(P):
+                vec[p] = vec[p] + src[p]
+        new[v] = vec
+    freq = np.array(new, dtype=np.float64).reshape(V, P)
+    return freq, {"total": total, "delta": delta, "matched": matched, "zero_full": zero_full, "n_full": F}
+
+
+def em_fixed_support(imputation, lines_or_path, config, iterations, block_lines=65536, planb=None, em=True, tol=None):
+    """EM on a fixed support: `iterations` times the M-step over the input (the block loop of `m_step_counts`, one
+    accumulator per iteration) followed by Graph.refresh on the accumulator, all on the device: no frequency file, no graph
+    regeneration, no upload.  -> a list of per-iteration dicts: the M-step statistics (subjects_used, skipped_plan_c,
+    contributions, rehashes, entries, spill, blocks, kernel_ms) and of the refresh total, delta, matched, zero_full, n_full,
+    outside = entries - matched (counters of haplotypes outside the support, which take no part) and refresh_ms.  Stops
+    early when `tol` is given and an iteration's delta <= tol.  imputation.netGraph holds the last frequencies, on the
+    device and in arrays["freq"]."""
+    lines = read_lines(lines_or_path)
+    g = imputation.netGraph
+    n_slots = len(g.full_loci)
+    out = []
+    for _ in range(int(iterations)):
+        shared = Blocks(imputation, config, planb, True, em, output_haplotypes=True)
+        acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(imputation.populations))
+        try:
+            _, kernel_ms, n_blocks = _accumulate_blocks(imputation, shared, lines, block_lines, acc)
+            it = acc.stats()
+            it.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
+            rs = g.refresh(shared.ctx, acc)
+        finally:
+            acc.close()
+        it.update(total=rs["total"], delta=rs["delta"], matched=rs["matched"], zero_full=rs["zero_full"], n_full=rs["n_full"],
+                  outside=it["entries"] - rs["matched"], refresh_ms=rs["kernel_ms"])
+        out.append(it)
+        if tol is not None and rs["delta"] <= tol:
+            break
+    return out

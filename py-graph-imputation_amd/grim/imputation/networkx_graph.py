@@ -360,5 +360,23 @@ class Graph(object):
             self._dev[id(ctx)] = dg
         return dg
 
+    def refresh(self, ctx, acc_or_records):
+        """EM on a fixed support: new frequencies from M-step counts, computed where the graph lies on `ctx`'s device
+        (grim_graph_refresh, include/grim_hip.h).  `acc_or_records`: an EmAccumulator of that context, or (keys, pops, counts)
+        in EmAccumulator.export's order.  The device copy of `ctx` is refreshed in place, the new frequencies come down and
+        replace arrays["freq"] (a new array: `_freqs`, `adjs_query` and any later upload agree with the device), and the
+        cached device copies of other contexts are dropped, so they upload again on next use.  -> the statistics (a dict).
+        The caller guarantees that no batch or stream of this graph is in flight.  A refusal raises NativeError and changes
+        nothing."""
+        dg = self.device(ctx)
+        if isinstance(acc_or_records, nat.EmAccumulator):
+            stats = dg.refresh(acc_or_records)
+        else:
+            keys, pops, counts = acc_or_records
+            stats = dg.refresh_records(keys, pops, counts)
+        self.arrays["freq"] = dg.freq()
+        self._dev = {id(ctx): dg}
+        return stats
+
     def host_bytes(self):
         return sum(v.nbytes for v in self.arrays.values() if isinstance(v, np.ndarray))
