@@ -461,6 +461,40 @@ int grim_em_stats(const grim_em *em, uint64_t out[4]);
 uint64_t grim_em_last_unsupported(const grim_em *em);
 /* device time of the last grim_em_accumulate: its kernels between their own start/stop events */
 double grim_em_kernel_ms(const grim_em *em);
+/* ---- merging tables: the sharded M-step (csrc/grim_em.h has the same text) ----
+ * grim_em_accumulate's promise needs a batch's sums to start from the counters the batches before it left.  Accumulators that
+ * run at the same time -- one per rank -- cannot give that, so the sharded M-step has a contract of its own:
+ *   the input is cut into chunks of chunk_lines lines, chunk c = global lines [c * chunk_lines, ...), as grim_chunk_offsets
+ *     cuts it;
+ *   T_c = the table of chunk c alone: the M-step above over the chunk's lines into an empty accumulator (batch cuts inside the
+ *     chunk stay invisible); S_c = the chunk's spilled counts, (population, haplotype text) -> count, in the chunk's order;
+ *   count[k, p] = ((T_c0[k, p] + T_c1[k, p]) + T_c2[k, p]) + ...  fp64, no fma, over the chunks c0 < c1 < ... whose table
+ *     holds the entry (k, p), in ascending chunk number; the spilled counts fold the same way.  A first contribution may be
+ *     written +0.0 + x: every count is >= +0.0, so these are the same bits.
+ * The answer depends on chunk_lines.  It does not depend on the number of ranks, on which rank ran which chunk, on the order
+ * in which the tables arrive, or on the batch cuts; with one chunk it is grim_em_accumulate's, bit for bit.  The statistics
+ * are the sums over the chunks.  The caller folds: it calls one of the two doors below once per chunk, in chunk order.
+ *
+ * grim_em_merge(dst, src): every entry of src's table into dst where both lie, no host trip.  One lane per slot of src; for
+ *   every set bit p of the slot's popmask the key is found or inserted in dst and dst.count[k, p] = dst.count[k, p] + src.count[k, p].
+ * grim_em_merge_records(dst, keys, pops, counts, n): the same add for an exported table, host arrays in grim_em_export's
+ *   order, uploaded, one lane per entry.  Both doors add through one device function.
+ * Keys are unique within src and (key, pop) pairs within an exported table, so each counter of dst is written by exactly one
+ * lane of a call: no floating-point atomics, no order inside a call.  Before the launch dst makes room by its own rule (keys
+ * in use plus incoming keys <= capacity / 2), doubling as grim_em_accumulate does; the doublings count in grim_em_stats
+ * out[3].  A probe that finds no slot all the same answers -1 ("the haplotype table overflowed").
+ * Refusals answer -3 with a grim_last_error text, launch nothing and change no bit of dst (grim_em_merge_ms is cleared
+ * first): src == dst; src belongs to another context, has another number of populations or another n_alleles; records
+ * door: a null array with n > 0, pops[i] >= n_pops, a key with a bit at or above GRIM_KEY_GRAPH_ORDER, a key field above
+ * n_alleles of its slot (an exported table never holds a private allele), entries not strictly ascending in (key, pop), a
+ * count that is negative, NaN or infinite -- the checks and texts of grim_graph_refresh_records where they are the same.
+ * A merge is not a batch: spill ordinals, grim_em_stats out[0..2], grim_em_last_unsupported and grim_em_kernel_ms do not
+ * move.  src's spill list is NOT merged: the caller folds it by allele text, in chunk order.  src is not changed. */
+int grim_em_merge(grim_em *dst, grim_em *src);
+int grim_em_merge_records(grim_em *dst, const uint64_t *keys, const uint32_t *pops, const double *counts, uint64_t n);
+/* device time of the last merge: its kernel, and the doublings before it, between their own start/stop events; 0.0 after a
+ * refusal or a merge of nothing.  grim_em_kernel_ms keeps speaking of the last grim_em_accumulate. */
+double grim_em_merge_ms(const grim_em *em);
 void grim_em_free(grim_em *em);
 
 /* ======================= EM on a fixed support: the graph's frequencies from M-step counts (csrc/grim_refresh.h) =======
@@ -486,7 +520,9 @@ void grim_em_free(grim_em *em);
  * population without any count inside the support; `stats` then holds the totals and n_full, everything else 0).
  * The new values are computed into a shadow buffer and committed in place, at the same device addresses, after the totals were
  * read.  The caller guarantees that no batch or stream of this graph is in flight; the call synchronises the context's stream
- * before its first launch and before it returns.  No floor, no pseudo-count, no new haplotypes, one device's counts. */
+ * before its first launch and before it returns.  No floor, no pseudo-count, no new haplotypes.  The counts of several
+ * devices come in as one table: their chunk tables folded in chunk order (grim_em_merge_records), then this call's records
+ * door on every device. */
 #define GRIM_REFRESH_BLOCK 4096 /* positions of one block of the totals' two-level fold */
 typedef struct {
   double total[GRIM_MAXPOP]; /* T_p */

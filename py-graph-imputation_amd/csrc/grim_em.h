@@ -19,6 +19,30 @@
 //   em_sum_kernel      one lane per run: counter = ((counter + w) + w) + ...
 // A haplotype that holds an allele the dictionary does not know (an id private to its subject, grim_hip.h grim_tokenize) can
 // never equal a dictionary-only one; its contributions go to a spill list the host folds by allele TEXT.
+//
+// The sharded M-step: a contract of its own.  The promise above holds because a batch's sums start from the counters the
+// batches before it left; accumulators that run at the same time (one per rank, grim/shard.py) cannot give that, so their
+// tables are MERGED, and the order of every sum is stated anew:
+//   the input is cut into chunks of chunk_lines lines, chunk c = global lines [c * chunk_lines, ...) (as chunk_offsets cuts it);
+//   T_c = the table of chunk c alone: the M-step above over the chunk's lines into an EMPTY accumulator (the block cuts
+//     inside a chunk stay invisible); S_c = the chunk's spilled counts, (population, haplotype text) -> count, folded in
+//     the chunk's contract order;
+//   count[k, p] = ((T_c0[k, p] + T_c1[k, p]) + T_c2[k, p]) + ...  fp64, no fma, over the chunks c0 < c1 < ... whose table
+//     holds the entry (k, p), in ascending chunk number; the spilled counts fold the same way.  A first contribution may be
+//     written +0.0 + x: every count is >= +0.0, so these are the same bits.
+// The answer depends on chunk_lines.  It does not depend on the number of ranks, on which rank ran which chunk, on the order
+// in which tables arrive (they are folded by chunk number), or on block_lines; with one chunk it is the M-step above, bit
+// for bit.  The statistics (subjects used, skipped for Plan C, contributions, spill) are the sums over the chunks.
+//
+// Two merge doors add a table to an accumulator (dst.counts[k, p] = dst.counts[k, p] + x, through ONE device function):
+//   em_merge_kernel          one lane per slot of the source accumulator's table, where both tables lie: for every set bit p
+//                            of the slot's popmask the key is found or inserted in dst and the counter added
+//   em_merge_records_kernel  one lane per entry of an exported table keys / pops / counts [n] (grim_em_export's order)
+// Keys are unique within a source, (key, population) pairs within an exported table: each dst counter is written by exactly
+// one lane of a call, so no floating-point atomics and no order inside a call; the order BETWEEN calls is the caller's (the
+// fold above calls in chunk order).  The host makes room first by the accumulator's own rule (used + incoming keys <=
+// cap / 2, em_rehash).  A merge is not a batch: spill records, their ordinals and the subject statistics do not move, and
+// the source's spill list is not merged (the host folds it by text).
 #pragma once
 #include "grim_dev.h"
 
@@ -234,6 +258,51 @@ __global__ __launch_bounds__(256) void em_sum_kernel(const uint32_t *grp, const 
   const uint32_t slot = g / T.P, pop = g - slot * T.P;
   const unsigned long long bit = 1ull << pop;
   if (!(atomicOr(T.popmask + slot, bit) & bit)) atomicAdd(stat + EM_S_ENTRIES, 1ull);
+}
+
+// ---- merge: one accumulator's table, or an exported one, added to another ---------------------------------------------------
+// the add both merge doors share: entry (slot t of D, population p) takes x.  Keys are unique within a source and the
+// (key, population) pairs of an exported table are, so exactly one lane of a launch writes a counter: a plain read, one
+// fp64 add, a plain write.  A counter that was never added to holds +0.0.
+__device__ __forceinline__ void em_merge_add(const EmTable &D, uint32_t t, uint32_t p, double x, unsigned long long *stat) {
+  const uint64_t at = (uint64_t)t * D.P + p;
+  D.counts[at] = D.counts[at] + x;
+  const unsigned long long bit = 1ull << p;
+  if (!(atomicOr(D.popmask + t, bit) & bit)) atomicAdd(stat + EM_S_ENTRIES, 1ull);
+}
+
+// one lane per slot of S: every entry of the slot into D
+__global__ __launch_bounds__(256) void em_merge_kernel(EmTable S, EmTable D, unsigned long long *stat) {
+  const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+  if (s > S.mask) return;
+  const unsigned long long word = S.keys[s];
+  unsigned long long m = S.popmask[s];
+  if (word == 0ull || m == 0ull) return;
+  const uint32_t t = em_find_or_insert(D, word & ~GRIM_VALID, stat);
+  if (t == GRIM_EM_NONE) {
+    atomicAdd(stat + EM_S_FAULT, 1ull);
+    return;
+  }
+  while (m) {
+    const uint32_t p = (uint32_t)__ffsll(m) - 1u;
+    m &= m - 1ull;
+    if (p < S.P && p < D.P) em_merge_add(D, t, p, S.counts[(uint64_t)s * S.P + p], stat);
+  }
+}
+
+// one lane per entry of keys / pops / counts [n] (the host has checked them): the entry into D
+__global__ __launch_bounds__(256) void em_merge_records_kernel(const unsigned long long *keys, const uint32_t *pops, const double *counts,
+                                                               uint32_t n, EmTable D, unsigned long long *stat) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t p = pops[i];
+  if (p >= D.P) return;
+  const uint32_t t = em_find_or_insert(D, keys[i], stat);
+  if (t == GRIM_EM_NONE) {
+    atomicAdd(stat + EM_S_FAULT, 1ull);
+    return;
+  }
+  em_merge_add(D, t, p, counts[i], stat);
 }
 
 // every entry of `from` into `to` (twice the size, zeroed), counters carried

@@ -1923,6 +1923,49 @@ struct RecordsUpload {
   }
 };
 
+// the door of a consumer that is given an exported table keys / pops / counts [n] in grim_em_export's order; `whose` names
+// the owner of n_pops in the text ("the graph's").  n_alleles, when given, bounds the fields of a key.  *distinct, when
+// given, takes the number of different keys.  The caller returns -3.
+static bool counts_door(grim_ctx *c, const char *who, const char *whose, uint32_t n_pops, const uint32_t *n_alleles, const uint64_t *keys,
+                        const uint32_t *pops, const double *counts, uint64_t n, uint64_t *distinct) {
+  if (n && (!keys || !pops || !counts)) return refuse(c, who, "a null array with n > 0");
+  uint64_t nd = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (pops[i] >= n_pops) return refuse(c, who, (std::string("a population at or above ") + whose + " number of populations").c_str());
+    if (keys[i] >> GRIM_KEY_GRAPH_ORDER) return refuse(c, who, "a key with a bit at or above GRIM_KEY_GRAPH_ORDER");
+    if (n_alleles)
+      for (int q = 0; q < GRIM_MAXL; ++q)
+        if ((uint32_t)((keys[i] >> (GRIM_ABITS * q)) & 0xFFFu) > n_alleles[q])
+          return refuse(c, who, "a key with a field above n_alleles of its slot (an exported table never holds a private allele)");
+    if (i && !(keys[i - 1] < keys[i] || (keys[i - 1] == keys[i] && pops[i - 1] < pops[i])))
+      return refuse(c, who, "the entries are not strictly ascending in (key, pop)");
+    if (!(counts[i] >= 0.0 && counts[i] <= 1.7976931348623157e308)) return refuse(c, who, "a count that is negative, NaN or infinite");
+    nd += i == 0 || keys[i - 1] != keys[i];
+  }
+  if (distinct) *distinct = nd;
+  return true;
+}
+
+// an exported table on the device, kept and grown
+struct CountsUpload {
+  DevBuf<unsigned long long> keys;
+  DevBuf<uint32_t> pops;
+  DevBuf<double> counts;
+  int upload(grim_ctx *c, const char *who, const uint64_t *h_keys, const uint32_t *h_pops, const double *h_counts, uint64_t n) {
+    if (!keys.reserve(n + 1) || !pops.reserve(n + 1) || !counts.reserve(n + 1)) {  // never an empty allocation
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    if (n) {
+      HIPCHK(hipMemcpyAsync(keys, h_keys, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+      HIPCHK(hipMemcpyAsync(pops, h_pops, 4 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+      HIPCHK(hipMemcpyAsync(counts, h_counts, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
+      HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+    }
+    return 0;
+  }
+};
+
 // a statistics block of the device (SLICES copies of COUNT words), slices added up; ends in a stream synchronise
 template <uint32_t COUNT, uint32_t SLICES>
 static int read_stat(grim_ctx *c, const unsigned long long *d_stat, uint64_t h[COUNT]) {
@@ -1956,11 +1999,12 @@ struct grim_em {
   DevBuf<double> d_w, d_ws;
   DevBuf<EmSpill> d_spill;
   RecordsUpload in;            // the uploaded records of grim_em_accumulate_records
+  CountsUpload merge_in;       // the uploaded table of grim_em_merge_records
   std::vector<EmSpill> spill;  // every batch's records, in contract order
   uint64_t table_used, entries, n_used, n_planc, n_contrib, n_rehash, last_unsupported;
   uint32_t batch_no;
-  Events<6> ev;
-  double last_ms;
+  Events<8> ev;  // 0..3 a batch, 4..5 a rehash, 6..7 a merge
+  double last_ms, merge_ms;
 };
 
 static void em_table_free(EmTable &T) {
@@ -2167,6 +2211,75 @@ extern "C" int grim_em_accumulate_records(grim_em *e, const grim_subject_result 
   return em_run(e, "grim_em_accumulate_records", e->in.res, e->in.rows, n_subjects, (uint32_t)n_rows);
 }
 
+// the launch behind both merge doors: room for `incoming` keys first, then one lane per slot of S (n == 0) or per entry of
+// the uploaded table
+static int em_merge_run(grim_em *e, const char *who, const EmTable *S, uint64_t incoming, uint32_t n) {
+  grim_ctx *c = e->ctx;
+  hipStream_t st = c->stream;
+  const std::string name(who);
+  double total_ms = 0.0;
+  while (e->table_used + incoming > e->cap / 2) {
+    const double r = em_rehash(e, name);
+    if (r < 0) return -1;
+    total_ms += r;
+  }
+  HIPCHK(hipMemsetAsync(e->d_stat + EM_S_FAULT, 0, 8, st), c, -1);
+  HIPCHK(hipEventRecord(e->ev[6], st), c, -1);
+  if (S)
+    hipLaunchKernelGGL(em_merge_kernel, dim3((S->mask + 256u) / 256u), dim3(256), 0, st, *S, e->T, e->d_stat);
+  else
+    hipLaunchKernelGGL(em_merge_records_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, e->merge_in.keys, e->merge_in.pops,
+                       e->merge_in.counts, n, e->T, e->d_stat);
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(e->ev[7], st), c, -1);
+  uint64_t h[EM_S_COUNT];
+  if (read_stat<EM_S_COUNT, 1>(c, e->d_stat, h) != 0) return -1;
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, e->ev[6], e->ev[7]), c, -1);
+  e->merge_ms = total_ms + ms;
+  if (h[EM_S_FAULT]) {
+    set_err(c, name + ": the haplotype table overflowed (internal)");
+    return -1;
+  }
+  e->table_used = h[EM_S_TABLE];
+  e->entries = h[EM_S_ENTRIES];
+  return 0;
+}
+
+extern "C" int grim_em_merge(grim_em *dst, grim_em *src) {
+  if (!dst || !src) return -1;
+  grim_ctx *c = dst->ctx;
+  const char *who = "grim_em_merge";
+  dst->merge_ms = 0.0;
+  if (src == dst) return refuse(c, who, "the source is the destination"), -3;
+  if (src->ctx != c) return refuse(c, who, "the accumulator belongs to another context"), -3;
+  if (src->T.P != dst->T.P) return refuse(c, who, "the accumulator has another number of populations"), -3;
+  for (int q = 0; q < GRIM_MAXL; ++q)
+    if (src->lim.n_alleles[q] != dst->lim.n_alleles[q]) return refuse(c, who, "the accumulator has another n_alleles"), -3;
+  use_device(c->device);
+  if (src->entries == 0) return 0;
+  return em_merge_run(dst, who, &src->T, src->table_used, 0);
+}
+
+extern "C" int grim_em_merge_records(grim_em *e, const uint64_t *keys, const uint32_t *pops, const double *counts, uint64_t n) {
+  if (!e) return -1;
+  grim_ctx *c = e->ctx;
+  const char *who = "grim_em_merge_records";
+  e->merge_ms = 0.0;
+  uint64_t distinct = 0;
+  if (!counts_door(c, who, "the accumulator's", e->T.P, e->lim.n_alleles, keys, pops, counts, n, &distinct)) return -3;
+  use_device(c->device);
+  if (n == 0) return 0;
+  if (n > 0x7FFFFFFFull) {  // strictly ascending entries of at most P populations a key: more than any table holds
+    set_err(c, std::string(who) + ": the table cannot grow beyond 2^31 counters");
+    return -1;
+  }
+  if (e->merge_in.upload(c, who, keys, pops, counts, n) != 0) return -1;
+  return em_merge_run(e, who, nullptr, distinct, (uint32_t)n);
+}
+
+extern "C" double grim_em_merge_ms(const grim_em *e) { return e ? e->merge_ms : 0.0; }
+
 extern "C" uint64_t grim_em_entries(const grim_em *e) { return e ? e->entries : 0; }
 extern "C" uint64_t grim_em_spill_count(const grim_em *e) { return e ? e->spill.size() : 0; }
 extern "C" uint64_t grim_em_last_unsupported(const grim_em *e) { return e ? e->last_unsupported : 0; }
@@ -2231,9 +2344,7 @@ struct RefreshState {
   DevBuf<uint32_t> d_short, d_long;  // the partial nodes by row length
   DevBuf<double> d_c, d_bsum, d_total, d_shadow;
   DevBuf<unsigned long long> d_stat;
-  DevBuf<unsigned long long> d_keys;  // the uploaded records of grim_graph_refresh_records
-  DevBuf<uint32_t> d_pops;
-  DevBuf<double> d_counts;
+  CountsUpload in;  // the uploaded records of grim_graph_refresh_records
   Events<4> ev;
 };
 
@@ -2353,33 +2464,17 @@ extern "C" int grim_graph_refresh_records(grim_graph *g, const uint64_t *keys, c
   const char *who = "grim_graph_refresh_records";
   if (stats) memset(stats, 0, sizeof(*stats));
   if (!g->refreshable) return refuse(c, who, ("the graph is not refreshable: " + g->refresh_why).c_str()), -3;
-  if (n && (!keys || !pops || !counts)) return refuse(c, who, "a null array with n > 0"), -3;
-  for (uint64_t i = 0; i < n; ++i) {
-    if (pops[i] >= g->d.P) return refuse(c, who, "a population at or above the graph's number of populations"), -3;
-    if (keys[i] >> GRIM_KEY_GRAPH_ORDER) return refuse(c, who, "a key with a bit at or above GRIM_KEY_GRAPH_ORDER"), -3;
-    if (i && !(keys[i - 1] < keys[i] || (keys[i - 1] == keys[i] && pops[i - 1] < pops[i])))
-      return refuse(c, who, "the entries are not strictly ascending in (key, pop)"), -3;
-    if (!(counts[i] >= 0.0 && counts[i] <= 1.7976931348623157e308)) return refuse(c, who, "a count that is negative, NaN or infinite"), -3;
-  }
+  if (!counts_door(c, who, "the graph's", g->d.P, nullptr, keys, pops, counts, n, nullptr)) return -3;
   use_device(c->device);
   if (!refresh_state(g, who)) return -1;
   RefreshState &R = *g->rf;
-  if (!R.d_keys.reserve(n + 1) || !R.d_pops.reserve(n + 1) || !R.d_counts.reserve(n + 1)) {
-    set_err(c, std::string(who) + ": device allocation failed");
-    return -1;
-  }
-  if (n) {
-    HIPCHK(hipMemcpyAsync(R.d_keys, keys, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
-    HIPCHK(hipMemcpyAsync(R.d_pops, pops, 4 * n, hipMemcpyHostToDevice, c->stream), c, -1);
-    HIPCHK(hipMemcpyAsync(R.d_counts, counts, 8 * n, hipMemcpyHostToDevice, c->stream), c, -1);
-    HIPCHK(hipStreamSynchronize(c->stream), c, -1);
-  }
+  if (R.in.upload(c, who, keys, pops, counts, n) != 0) return -1;
   RfCounts C;
   memset(&C, 0, sizeof(C));
   C.records = 1;
-  C.keys = R.d_keys;
-  C.pops = R.d_pops;
-  C.counts = R.d_counts;
+  C.keys = R.in.keys;
+  C.pops = R.in.pops;
+  C.counts = R.in.counts;
   C.n = n;
   return refresh_run(g, who, C, stats);
 }

@@ -375,6 +375,7 @@ class DeviceBatch(_Handle):
 EXPORTS += [
     "grim_em_create", "grim_em_accumulate", "grim_em_accumulate_records", "grim_em_entries", "grim_em_export", "grim_em_spill_count",
     "grim_em_spill", "grim_em_stats", "grim_em_last_unsupported", "grim_em_kernel_ms", "grim_em_free",
+    "grim_em_merge", "grim_em_merge_records", "grim_em_merge_ms",
 ]
 
 SPILL_DT = np.dtype([("key", "<u8"), ("w", "<f8"), ("batch", "<u4"), ("subject", "<u4"), ("row", "<u4"), ("pop", "<u2"), ("side", "<u2")])
@@ -408,6 +409,12 @@ def _em_lib():
         L.grim_em_kernel_ms.restype = C.c_double
         L.grim_em_kernel_ms.argtypes = [C.c_void_p]
         L.grim_em_free.argtypes = [C.c_void_p]
+        L.grim_em_merge.restype = C.c_int
+        L.grim_em_merge.argtypes = [C.c_void_p, C.c_void_p]
+        L.grim_em_merge_records.restype = C.c_int
+        L.grim_em_merge_records.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.grim_em_merge_ms.restype = C.c_double
+        L.grim_em_merge_ms.argtypes = [C.c_void_p]
         _em_ready = True
     return L
 
@@ -469,6 +476,26 @@ class EmAccumulator(_Handle):
 
     def kernel_ms(self):
         return float(_em_lib().grim_em_kernel_ms(self.h))
+
+    def merge(self, other):
+        """every entry of `other`'s table added to this one's on the device (grim_em_merge); `other` is not changed, its spill
+        list is not merged.  The caller merges in chunk order: count = (count + other's), one add per entry."""
+        self._check(_em_lib().grim_em_merge(self.h, other.h), "grim_em_merge")
+
+    def merge_records(self, keys, pops, counts):
+        """the same add for an exported table: host arrays keys u64 / pops u32 / counts f64 in export()'s order"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        pops = np.ascontiguousarray(pops, dtype=np.uint32)
+        counts = np.ascontiguousarray(counts, dtype=np.float64)
+        if not (keys.ndim == 1 and keys.shape == pops.shape == counts.shape):
+            raise ValueError("keys, pops and counts must be one-dimensional and of one length")
+        n = keys.shape[0]
+        self._check(_em_lib().grim_em_merge_records(self.h, _ptr(keys) if n else None, _ptr(pops) if n else None,
+                                                    _ptr(counts) if n else None, n), "grim_em_merge_records")
+
+    def merge_ms(self):
+        """device time of the last merge (kernel_ms keeps speaking of the last accumulate)"""
+        return float(_em_lib().grim_em_merge_ms(self.h))
 
 
 # ---- marginal genotype tables (grim_marginal_*): the UMUG rows of finished batches reduced to a subset of the loci ----

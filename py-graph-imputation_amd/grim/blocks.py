@@ -48,11 +48,11 @@ class Blocks:
         """an open Block of `lines`, the first of which is line `lo` of the input; the caller closes it"""
         return Block(self, lines, lo)
 
-    def cut(self, lines, block_lines):
+    def cut(self, lines, block_lines, first=0):
         """`lines` in blocks of `block_lines`: yields each as an open Block and closes it when the caller comes back for the next
-        (or closes the generator)"""
+        (or closes the generator); `first`: the input line `lines` begins at"""
         for lo in range(0, len(lines), block_lines):
-            block = self.block(lines[lo:lo + block_lines], lo)
+            block = self.block(lines[lo:lo + block_lines], first + lo)
             try:
                 yield block
             finally:

@@ -16,6 +16,10 @@ Every counter is the left-to-right fp64 sum of its contributions in (line, rank,
 is copied to the host.  `fold_pmug_text` is the same fold over `.pmug` text in plain Python floats, `fold_records` the same
 over record arrays as `EmAccumulator.accumulate_records` takes them.  Device and twins agree bit for bit.  There is no CPU
 fallback of `m_step_counts`.
+
+`m_step_chunked` is the M-step by the sharded contract on one device: the input in chunks of `chunk_lines` lines,
+each chunk's table built in an empty accumulator, the tables merged on the device in chunk order; `merge_tables` and
+`fold_chunk_tables` are its CPU twins, `grim.shard.m_step_sharded` the same across ranks.
 """
 
 import gzip
@@ -144,17 +148,17 @@ def fold_records(res, rows, n_alleles, n_pops, batch=0, carry=None):
     return keys, pops, counts, np.array(spill, dtype=nat.SPILL_DT), stats
 
 
-def _accumulate_blocks(imputation, shared, lines, block_lines, acc):
+def _accumulate_blocks(imputation, shared, lines, block_lines, acc, first=0):
     """The block loop of the M-step: `lines` in blocks of `block_lines`, each tokenised, imputed as one device batch of
     `shared` (a Blocks) and added to the accumulator `acc` where its rows lie.  -> (spilled, kernel_ms, blocks); spilled:
     (pop index, haplotype text) -> count, the haplotypes that hold an allele the dictionary does not know.  Resets and fills
-    imputation.unsupported."""
+    imputation.unsupported; `first`: the input line `lines` begins at (unsupported subjects are reported by input line)."""
     n_slots = len(imputation.netGraph.full_loci)
     imputation.unsupported = []
     spilled = {}
     kernel_ms = 0.0
     n_blocks = 0
-    cut = shared.cut(lines, max(1, int(block_lines)))
+    cut = shared.cut(lines, max(1, int(block_lines)), first)
     try:
         for block in cut:
             bad = block.bad
@@ -177,6 +181,21 @@ def _accumulate_blocks(imputation, shared, lines, block_lines, acc):
     return spilled, kernel_ms, n_blocks
 
 
+def _counts_by_name(g, pops, table, spilled):
+    """an exported table (keys, pops, counts) and the spilled counts -> {pop: {haplotype: count}}"""
+    keys, kpops, vals = table
+    counts = {}
+    names = {}
+    for key, p, v in zip(keys.tolist(), kpops.tolist(), vals.tolist()):
+        name = names.get(key)
+        if name is None:
+            name = names[key] = "~".join(x for x in g.key_alleles(key) if x)
+        counts.setdefault(pops[p], {})[name] = v
+    for (p, name), v in spilled.items():
+        counts.setdefault(pops[p], {})[name] = v
+    return counts
+
+
 def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
     """The M-step on the device.  `lines_or_path`: input lines (a list) or the path of an input file; `config`: the
     configuration dict of `load_config`.  The input is cut into blocks of `block_lines` lines; each is tokenised, imputed
@@ -193,21 +212,148 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
     acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(pops), first_capacity)
     try:
         spilled, kernel_ms, n_blocks = _accumulate_blocks(imputation, shared, lines, block_lines, acc)
-        keys, kpops, vals = acc.export()
-        counts = {}
-        names = {}
-        for key, p, v in zip(keys.tolist(), kpops.tolist(), vals.tolist()):
-            name = names.get(key)
-            if name is None:
-                name = names[key] = "~".join(x for x in g.key_alleles(key) if x)
-            counts.setdefault(pops[p], {})[name] = v
-        for (p, name), v in spilled.items():
-            counts.setdefault(pops[p], {})[name] = v
+        counts = _counts_by_name(g, pops, acc.export(), spilled)
         stats = acc.stats()
         stats.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
     finally:
         acc.close()
     return counts, stats
+
+
+# ---- the sharded M-step: chunk tables folded in chunk order (the header comment of csrc/grim_em.h) -------------
+def merge_tables(carry, keys, pops, counts, n_pops=None, n_alleles=None):
+    """The CPU twin of grim_em_merge_records (and of grim_em_merge on the table the source would export) in plain Python
+    floats: every entry of keys / pops / counts [n] (EmAccumulator.export's order) added to `carry`, a (key, pop) -> count
+    dict that is updated in place and returned: carry[k, p] = carry[k, p] + x, a first contribution as +0.0 + x.  The
+    refusals of the device call are raised as ValueError, before `carry` is touched; the checks on populations need
+    `n_pops`, those on key fields `n_alleles` (the accumulator's), and are left out where that is None."""
+    if keys is None or pops is None or counts is None:
+        raise ValueError("a null array")
+    K = [int(k) for k in np.asarray(keys).tolist()]
+    Q = [int(q) for q in np.asarray(pops).tolist()]
+    X = [float(x) for x in np.asarray(counts).tolist()]
+    if not len(K) == len(Q) == len(X):
+        raise ValueError("keys, pops and counts of different lengths")
+    limits = None if n_alleles is None else [int(x) for x in n_alleles] + [0] * (nat.MAXL - len(n_alleles))
+    for i in range(len(K)):
+        k, q, x = K[i], Q[i], X[i]
+        if q < 0 or (n_pops is not None and q >= int(n_pops)):
+            raise ValueError("a population at or above the accumulator's number of populations")
+        if k < 0 or k >> 60:
+            raise ValueError("a key with a bit at or above bit 60")
+        if limits is not None and any(((k >> (nat.ABITS * s)) & 0xFFF) > limits[s] for s in range(nat.MAXL)):
+            raise ValueError("a key with a field above n_alleles of its slot")
+        if i and not (K[i - 1], Q[i - 1]) < (k, q):
+            raise ValueError("the entries are not strictly ascending in (key, pop)")
+        if not (x >= 0.0 and x != float("inf")):
+            raise ValueError("a count that is negative, NaN or infinite")
+    for k, q, x in zip(K, Q, X):
+        carry[(k, q)] = carry.get((k, q), 0.0) + x
+    return carry
+
+
+def table_arrays(table):
+    """a (key, pop) -> count dict -> (keys u64, pops u32, counts f64) in EmAccumulator.export's order"""
+    order = sorted(table)
+    return (np.array([k for k, _ in order], dtype=np.uint64), np.array([p for _, p in order], dtype=np.uint32),
+            np.array([table[at] for at in order], dtype=np.float64))
+
+
+def fold_chunk_tables(tables, n_pops=None, n_alleles=None):
+    """The chunk-ordered fold: `tables` is the list, in chunk order, of the chunks' exported tables (keys, pops, counts);
+    count[k, p] = ((T_c0[k, p] + T_c1[k, p]) + T_c2[k, p]) + ... over the chunks that hold the entry -> (keys, pops, counts) in
+    export order."""
+    carry = {}
+    for keys, pops, counts in tables:
+        merge_tables(carry, keys, pops, counts, n_pops, n_alleles)
+    return table_arrays(carry)
+
+
+def fold_spilled(master, spilled):
+    """a chunk's spilled counts (pop index, haplotype text) -> count added to `master` (in place), as the tables fold"""
+    for at, v in spilled.items():
+        master[at] = master[at] + v if at in master else v
+    return master
+
+
+CHUNK_STATS = ("subjects_used", "skipped_plan_c", "contributions", "rehashes", "spill", "blocks", "kernel_ms")
+
+
+def chunk_table(imputation, shared, lines, line_offset, block_lines=65536, first_capacity=1 << 20):
+    """The chunk-local part of the sharded M-step: today's M-step over one chunk's `lines` (the first is input line
+    `line_offset`) into a fresh accumulator -> (the accumulator, open: the caller closes it; spilled; stats, the keys of
+    CHUNK_STATS; the chunk's unsupported subjects)."""
+    g = imputation.netGraph
+    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]
+    acc = nat.EmAccumulator(shared.ctx, n_alleles, len(imputation.populations), first_capacity)
+    try:
+        spilled, kernel_ms, n_blocks = _accumulate_blocks(imputation, shared, lines, block_lines, acc, line_offset)
+        stats = acc.stats()
+        stats.update(spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
+    except BaseException:
+        acc.close()
+        raise
+    return acc, spilled, stats, list(imputation.unsupported)
+
+
+def chunk_text_lines(raw):
+    """a chunk's bytes -> its lines without line ends, as `read_lines` reads a file's"""
+    import io
+
+    return io.TextIOWrapper(io.BytesIO(raw), encoding="utf-8", newline=None).read().splitlines()
+
+
+def input_chunks(lines_or_path, chunk_lines):
+    """(first input line, lines) of every chunk of `chunk_lines` lines.  A file is cut where grim.shard.chunk_offsets cuts it
+    for impute_sharded and m_step_sharded; a list by its index."""
+    if isinstance(lines_or_path, (str, bytes, os.PathLike)):
+        offs = nat.chunk_offsets(os.fspath(lines_or_path), chunk_lines)
+        with open(lines_or_path, "rb") as fh:
+            for c in range(len(offs) - 1):
+                fh.seek(offs[c])
+                yield c * chunk_lines, chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
+    else:
+        lines = read_lines(lines_or_path)
+        for lo in range(0, len(lines), chunk_lines):
+            yield lo, lines[lo:lo + chunk_lines]
+
+
+def m_step_chunked(imputation, lines_or_path, config, chunk_lines, block_lines=65536, planb=None, em=True, first_capacity=1 << 20):
+    """The sharded M-step's single-process definition, on one device: the input in chunks of `chunk_lines` lines, each
+    chunk's M-step into a fresh accumulator (`chunk_table`), the chunks' tables merged on the device into a master
+    accumulator in chunk order (EmAccumulator.merge), the spilled counts folded in chunk order.  -> (counts, stats, table):
+    counts and stats shaped like `m_step_counts`' (stats are the sums over the chunks; `entries` the master's; `rehashes`
+    the chunks' and the master's; plus `chunks` and `merge_ms`), table = the master's (keys, pops, counts) as
+    Graph.refresh takes them.  The counts depend on chunk_lines and not on block_lines; with one chunk they are
+    `m_step_counts`', bit for bit.  imputation.unsupported holds every chunk's subjects, by input line."""
+    chunk_lines = max(1, int(chunk_lines))
+    g = imputation.netGraph
+    pops = imputation.populations
+    shared = Blocks(imputation, config, planb, True, em, output_haplotypes=True)
+    master = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(len(g.full_loci))], len(pops), first_capacity)
+    stats = dict.fromkeys(CHUNK_STATS, 0)
+    stats.update(kernel_ms=0.0, merge_ms=0.0, chunks=0)
+    spilled, unsupported = {}, []
+    try:
+        for lo, lines in input_chunks(lines_or_path, chunk_lines):
+            acc, chunk_spilled, chunk_stats, bad = chunk_table(imputation, shared, lines, lo, block_lines, first_capacity)
+            try:
+                master.merge(acc)
+            finally:
+                acc.close()
+            fold_spilled(spilled, chunk_spilled)
+            for k in CHUNK_STATS:
+                stats[k] += chunk_stats[k]
+            stats["merge_ms"] += master.merge_ms()
+            stats["chunks"] += 1
+            unsupported += bad
+        imputation.unsupported = unsupported
+        table = master.export()
+        stats["rehashes"] += master.stats()["rehashes"]
+        stats["entries"] = master.entries()
+    finally:
+        master.close()
+    return _counts_by_name(g, pops, table, spilled), stats, table
 
 
 def write_freq_files(counts, freq_data_dir, pops):

@@ -22,6 +22,10 @@ The only communication is the control plane: an atomic fetch-add on the job's re
 the job's id, six sizes per chunk, one barrier at the end, and an error slot per rank so that a rank that fails does not
 leave the others waiting.
 
+The M-step and the fixed-support EM shard the same way (`m_step_sharded`, `em_fixed_support_sharded`): ranks
+pull chunks, each chunk's count table is built in a fresh accumulator on the rank's GPU and published on the store as bytes,
+rank 0 folds the tables in CHUNK order (EmAccumulator.merge_records) and publishes the one result every rank returns.
+
 Launch:  torchrun --nproc-per-node N --master-addr 127.0.0.1 your_script.py   ->  impute_sharded(conf)
 (`impute_sharded` joins the job itself -- gloo, control plane only -- when the caller has not initialised
 torch.distributed; alone, without WORLD_SIZE > 1, it runs every chunk in this process).
@@ -69,9 +73,12 @@ class _PeerFailed(RuntimeError):
 class _Control:
     """the job's control plane: chunk counter, shared values, error slots, final barrier"""
 
-    def __init__(self):
+    def __init__(self, timeout_s=None):
+        """timeout_s: every wait_key / wait_bytes / share of this control plane ends with a TimeoutError that many seconds
+        from now (None: a wait ends when its key is set or a peer reports an error)"""
         self.rank, self.world, self.dist, self.store = 0, 1, None, None
         self.local = 0
+        self.deadline = None if timeout_s is None else time.monotonic() + float(timeout_s)
         world_env = int(os.environ.get("WORLD_SIZE", "1"))
         try:
             import torch.distributed as dist
@@ -111,6 +118,8 @@ class _Control:
             v = make()
             self.store.set(key, v)
             return v
+        if self.deadline is not None:
+            return self.wait_key(key, None)
         return self.store.get(key).decode()
 
     def set(self, key, value):
@@ -119,18 +128,32 @@ class _Control:
 
     def wait_key(self, key, tag, poll=0.0005):
         """the value of a key some rank will set -- POLLED (a blocking get would hold the store client, and with it this
-        rank's chunk counter, for as long as it waits); raises when a rank has reported an error meanwhile"""
+        rank's chunk counter, for as long as it waits); raises when a rank has reported an error meanwhile (`tag` None:
+        the job has no id yet, so no error slot either), or when the control plane's deadline has passed"""
+        return self.wait_bytes(key, tag, poll).decode()
+
+    def wait_bytes(self, key, tag, poll=0.0005):
+        """wait_key, the value as the bytes the store holds"""
         last_look = 0.0
         while True:
             if self._has(key):
-                return self.store.get(key).decode()
+                return self.store.get(key)
             now = time.monotonic()
             if now - last_look > 0.05:
                 last_look = now
                 for r in range(self.world):
-                    if r != self.rank and self._has("grim_err_%s_%d" % (tag, r)):
+                    if tag is not None and r != self.rank and self._has("grim_err_%s_%d" % (tag, r)):
                         raise _PeerFailed("rank %d failed while this rank was waiting for %s" % (r, key))
+                if self.deadline is not None and now > self.deadline:
+                    raise TimeoutError("no rank has set %s within the job's timeout" % key)
             time.sleep(poll)
+
+    def delete(self, key):
+        if self.store is not None:
+            try:
+                self.store.delete_key(key)
+            except Exception:  # a store that cannot delete keeps the key: it carries the job's id and is never read again
+                pass
 
     def report_error(self, tag, text):
         if self.store is not None:
@@ -450,6 +473,245 @@ def impute_sharded(conf_file, hap_pop_pair=False, graph=None, compute=None, proj
                 with open(config[names[k][0]]) as fh:
                     result[k] = fh.read()
     return result
+
+
+# ---- the sharded M-step: every chunk's table onto the store, folded by rank 0 in chunk order ---------------------
+PIECE_BYTES = 4 << 20  # the most one store key carries: the store's own value limit has not been measured
+
+
+def _pack_table(keys, pops, counts, spilled, stats, unsupported):
+    """a chunk's (or the job's) result as bytes: a JSON head (floats as hex: every bit travels) and the three arrays"""
+    import struct
+
+    import numpy as np
+
+    keys = np.ascontiguousarray(keys, dtype="<u8")
+    pops = np.ascontiguousarray(pops, dtype="<u4")
+    counts = np.ascontiguousarray(counts, dtype="<f8")
+    head = json.dumps({"n": int(keys.shape[0]), "stats": stats, "unsupported": [list(u) for u in unsupported],
+                       "spilled": [[int(p), name, float(v).hex()] for (p, name), v in spilled.items()]}).encode()
+    return struct.pack("<Q", len(head)) + head + keys.tobytes() + pops.tobytes() + counts.tobytes()
+
+
+def _unpack_table(blob):
+    import struct
+
+    import numpy as np
+
+    (n_head,) = struct.unpack_from("<Q", blob, 0)
+    head = json.loads(blob[8:8 + n_head].decode())
+    n, at = head["n"], 8 + n_head
+    if len(blob) != at + 20 * n:
+        raise RuntimeError("m_step_sharded: a table of %d entries in %d bytes" % (n, len(blob) - at))
+    keys = np.frombuffer(blob, dtype="<u8", count=n, offset=at).copy()
+    pops = np.frombuffer(blob, dtype="<u4", count=n, offset=at + 8 * n).copy()
+    counts = np.frombuffer(blob, dtype="<f8", count=n, offset=at + 12 * n).copy()
+    spilled = {(int(p), name): float.fromhex(v) for p, name, v in head["spilled"]}  # (insertion order = the sender's)
+    return keys, pops, counts, spilled, head["stats"], [tuple(u) for u in head["unsupported"]]
+
+
+def _publish(ctl, name, blob):
+    """blob under `name`: pieces of at most PIECE_BYTES, then the head key that says how many (set last: who sees it finds
+    every piece)"""
+    n = max(1, -(-len(blob) // PIECE_BYTES))
+    for i in range(n):
+        ctl.set("%s_%d" % (name, i), blob[i * PIECE_BYTES:(i + 1) * PIECE_BYTES])
+    ctl.set(name, str(n))
+
+
+def _collect(ctl, name, tag, delete):
+    n = int(ctl.wait_key(name, tag))
+    blob = b"".join(ctl.wait_bytes("%s_%d" % (name, i), tag) for i in range(n))
+    if delete:
+        for i in range(n):
+            ctl.delete("%s_%d" % (name, i))
+        ctl.delete(name)
+    return blob
+
+
+def _names_of(keys, pops, counts, spilled, pop_names, hap_name):
+    out = {}
+    names = {}
+    for key, p, v in zip(keys.tolist(), pops.tolist(), counts.tolist()):
+        name = names.get(key)
+        if name is None:
+            name = names[key] = hap_name(key)
+        out.setdefault(pop_names[p] if p < len(pop_names) else str(p), {})[name] = v
+    for (p, name), v in spilled.items():
+        out.setdefault(pop_names[p] if p < len(pop_names) else str(p), {})[name] = v
+    return out
+
+
+M_STEP_SUMS = ("subjects_used", "skipped_plan_c", "contributions", "rehashes", "spill", "blocks", "kernel_ms")
+
+
+def m_step_sharded(conf_file, chunk_lines=None, graph=None, compute=None, timeout_s=1800, block_lines=65536):
+    """The M-step across the ranks of the torch.distributed job (or alone if there is none), by the chunk-ordered contract
+    of DESIGN 4.5: the input is cut into chunks of `chunk_lines` lines as `impute_sharded` cuts it, the ranks pull chunk
+    numbers from the job's counter, each runs a chunk's M-step on its own GPU into a fresh accumulator (grim.em.chunk_table)
+    and publishes the chunk's exported table, spilled counts, statistics and unsupported subjects on the job's store; rank 0
+    folds the tables in CHUNK order through EmAccumulator.merge_records into a master accumulator and publishes the result.
+    -> (counts, stats, table) on EVERY rank, the same bytes: counts {pop: {haplotype: count}} and stats as
+    grim.em.m_step_chunked returns them (plus stats["unsupported"]: the subjects of all ranks, by input line, that
+    GRIM_ON_UNSUPPORTED=skip let the job go on without), table = (keys, pops, counts) as Graph.refresh takes them.  The
+    answer depends on chunk_lines; not on the world size, on which rank ran which chunk, on the order the tables arrive in,
+    or on block_lines.  Alone it equals m_step_chunked.
+
+    `compute(config, lines, line_offset) -> (keys, pops, counts, spilled, stats)` can be injected (tests); the fold then
+    runs through grim.em.fold_chunk_tables and haplotypes are named by their key.  Every wait ends `timeout_s` seconds
+    after the call began at the latest, or when a peer reports an error; every rank raises when any rank failed."""
+    return _m_step_sharded(conf_file, chunk_lines, graph, compute, timeout_s, block_lines, None)
+
+
+def _m_step_sharded(conf_file, chunk_lines, graph, compute, timeout_s, block_lines, _state):
+    """m_step_sharded; `_state`: a dict that keeps the rank's Imputation (and with it its device graph) from call to call"""
+    from .em import chunk_text_lines
+    from .run_impute_def import load_config
+
+    ctl = _Control(timeout_s)
+    chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
+    error = peer_failed = None
+    result = None
+    tag = ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
+    master = None
+    try:
+        config, _ = load_config(conf_file)
+        in_path = config["imputation_input_file"]
+        offs = chunk_offsets(in_path, chunk_lines)
+        n_chunks = len(offs) - 1
+        imp = shared = None
+        if compute is None:
+            from . import _native as nat
+            from .blocks import Blocks
+            from .em import chunk_table
+            from .imputation.impute import Imputation as _I
+            from .imputation.networkx_graph import Graph
+
+            if _state is not None and _state.get("imp") is not None:
+                imp = _state["imp"]
+            else:
+                if graph is None:
+                    graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
+                n_dev = max(1, nat.lib().grim_device_count())
+                imp = _I(graph, config, device=ctl.local % n_dev)
+                if _state is not None:
+                    _state["imp"] = imp
+            shared = Blocks(imp, config, None, True, True, output_haplotypes=True)
+            pop_names = list(imp.populations)
+            hap_name = imp.netGraph.key_to_name
+        else:
+            pop_names = list(config.get("pops") or [])
+            hap_name = str
+        # ---- this rank's chunks ----------------------------------------------------------------------------------------
+        own = {}
+        with open(in_path, "rb") as fh:
+            while True:
+                c = ctl.next_chunk(tag)
+                if c >= n_chunks:
+                    break
+                fh.seek(offs[c])
+                lines = chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
+                if compute is None:
+                    acc, spilled, stats, bad = chunk_table(imp, shared, lines, c * chunk_lines, block_lines)
+                    try:
+                        keys, pops, counts = acc.export()
+                    finally:
+                        acc.close()
+                else:
+                    keys, pops, counts, spilled, stats = compute(config, lines, c * chunk_lines)
+                    bad = []
+                if ctl.rank == 0:
+                    own[c] = (keys, pops, counts, spilled, stats, bad)
+                else:
+                    _publish(ctl, "grim_emt_%s_%d" % (tag, c), _pack_table(keys, pops, counts, spilled, stats, bad))
+        # ---- rank 0: the fold, in chunk order --------------------------------------------------------------------------
+        final = "grim_emf_" + tag
+        if ctl.rank == 0:
+            from .em import fold_chunk_tables, fold_spilled
+
+            stats = dict.fromkeys(M_STEP_SUMS, 0)
+            stats.update(kernel_ms=0.0, merge_ms=0.0, chunks=n_chunks)
+            spilled, unsupported, tables = {}, [], []
+            if compute is None:
+                g = imp.netGraph
+                master = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(len(g.full_loci))], len(pop_names))
+            for c in range(n_chunks):
+                part = own.pop(c, None)
+                if part is None:
+                    part = _unpack_table(_collect(ctl, "grim_emt_%s_%d" % (tag, c), tag, True))
+                keys, pops, counts, chunk_spilled, chunk_stats, bad = part
+                if master is not None:
+                    master.merge_records(keys, pops, counts)
+                    stats["merge_ms"] += master.merge_ms()
+                else:
+                    tables.append((keys, pops, counts))
+                fold_spilled(spilled, chunk_spilled)
+                for k in M_STEP_SUMS:
+                    stats[k] += chunk_stats.get(k, 0)
+                unsupported += bad
+            if master is not None:
+                table = master.export()
+                stats["rehashes"] += master.stats()["rehashes"]
+            else:
+                table = fold_chunk_tables(tables)
+            stats["entries"] = int(table[0].shape[0])
+            blob = _pack_table(table[0], table[1], table[2], spilled, stats, sorted(unsupported))
+            if ctl.world > 1:
+                _publish(ctl, final, blob)
+        else:
+            blob = _collect(ctl, final, tag, False)
+        keys, pops, counts, spilled, stats, unsupported = _unpack_table(blob)  # every rank reads the same bytes
+        stats["unsupported"] = unsupported
+        result = (_names_of(keys, pops, counts, spilled, pop_names, hap_name), stats, (keys, pops, counts))
+    except BaseException as e:  # the other ranks must not wait for this one: report, reach the barrier, raise
+        if isinstance(e, _PeerFailed):
+            peer_failed = e
+        else:
+            error = e
+            ctl.report_error(tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
+    finally:
+        if master is not None:
+            master.close()
+    failed = ctl.barrier_and_errors(tag)
+    try:
+        if error is not None:
+            raise error
+        if failed:
+            raise RuntimeError("m_step_sharded: rank(s) %s failed:\n%s" % ([r for r, _ in failed], failed[0][1]))
+        if peer_failed is not None:
+            raise peer_failed
+    finally:
+        ctl.barrier()  # nobody leaves while another rank still reads the store
+        if ctl.rank == 0 and ctl.world > 1 and result is not None:
+            n = max(1, -(-len(blob) // PIECE_BYTES))
+            for i in range(n):
+                ctl.delete("grim_emf_%s_%d" % (tag, i))
+            ctl.delete("grim_emf_" + tag)
+    return result
+
+
+def em_fixed_support_sharded(conf_file, iterations, chunk_lines=None, tol=None, graph=None, timeout_s=1800, block_lines=65536):
+    """EM on a fixed support across the ranks of the job: per iteration `m_step_sharded`, then EVERY rank refreshes its own
+    device graph with Graph.refresh(ctx, (keys, pops, counts)) through the records door from the one published table --
+    rank 0 too, so that all ranks run the same code on the same numbers and hold the same frequencies, bit for bit.  The
+    decision to stop (`tol` given and the iteration's delta <= tol) is rank 0's, shared through the store.  -> the list of
+    per-iteration dicts of grim.em.em_fixed_support (kernel_ms etc. summed over the chunks) plus `chunks`, `merge_ms` and
+    `unsupported`, the same on every rank apart from `refresh_ms`."""
+    from . import _native as nat
+
+    state = {"imp": None}  # one Imputation, and with it one device graph, for every iteration
+    out = []
+    for _ in range(int(iterations)):
+        _, it, table = _m_step_sharded(conf_file, chunk_lines, graph, None, timeout_s, block_lines, state)
+        ctl, imp = _Control(timeout_s), state["imp"]
+        rs = imp.netGraph.refresh(nat.default_context(imp.device), table)
+        it.update(total=rs["total"], delta=rs["delta"], matched=rs["matched"], zero_full=rs["zero_full"], n_full=rs["n_full"],
+                  outside=it["entries"] - rs["matched"], refresh_ms=rs["kernel_ms"])
+        out.append(it)
+        stop = ctl.share("grim_emstop_%d" % _next_call(), lambda: "1" if tol is not None and rs["delta"] <= tol else "0")
+        if stop == "1":
+            break
+    return out
 
 
 _call_counter = [0]

@@ -1,10 +1,14 @@
 """
 Measure the device M-step (grim/em.py, csrc/grim_em.h) on bench.py's config-4-shaped workload: the pop4 graph, 100 000
-mixed subjects of seed 3, MR priors, em_mr on.  One JSON line with three medians over --steps steps after --warmup:
+mixed subjects of seed 3, MR priors, em_mr on.  One JSON line with medians over --steps steps after --warmup:
 
   (a) impute_kernel_ms   the batch's kernels, grim_batch_kernel_ms(GRIM_MS_TOTAL) in timing mode
   (b) em_kernel_ms       grim_em_kernel_ms of the accumulate call on that batch (a fresh accumulator every step)
   (c) text_route_s       what a caller had before: impute_lines_block text -> fold_pmug_text, wall time
+  (d) merge_ms           the sharded M-step's fold of that batch taken as ONE chunk: grim_em_merge_ms of merging the step's
+                         accumulator into an empty master where both tables lie (EmAccumulator.merge)
+  (e) merge_records_ms   the same chunk through the records door (EmAccumulator.merge_records of the exported table): device
+                         time, next to merge_records_wall_ms (check, upload and launch) and export_wall_ms (the sender's side)
 
     python tools/em_bench.py [--subjects N] [--steps K] [--warmup W]
 """
@@ -64,6 +68,7 @@ def main():
     batch.set_timing(True)
     n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]
     a_ms, b_ms, stats, entries = [], [], None, 0
+    d_ms, e_ms, e_wall, x_wall = [], [], [], []
     for step in range(args.warmup + args.steps):
         batch.run()
         acc = nat.EmAccumulator(ctx, n_alleles, P)
@@ -73,6 +78,24 @@ def main():
                 a_ms.append(batch.kernel_ms(nat.MS_TOTAL))
                 b_ms.append(acc.kernel_ms())
             stats, entries = acc.stats(), acc.entries()
+            master, by_records = nat.EmAccumulator(ctx, n_alleles, P), nat.EmAccumulator(ctx, n_alleles, P)
+            try:
+                master.merge(acc)
+                t0 = timeit.default_timer()
+                table = acc.export()
+                t1 = timeit.default_timer()
+                by_records.merge_records(*table)
+                t2 = timeit.default_timer()
+                if master.entries() != entries or by_records.entries() != entries:
+                    raise RuntimeError("a merge into an empty accumulator holds another number of entries than its source")
+                if step >= args.warmup:
+                    d_ms.append(master.merge_ms())
+                    e_ms.append(by_records.merge_ms())
+                    x_wall.append(1e3 * (t1 - t0))
+                    e_wall.append(1e3 * (t2 - t1))
+            finally:
+                master.close()
+                by_records.close()
         finally:
             acc.close()
     batch.close()
@@ -87,6 +110,8 @@ def main():
         "workload": "pop4 graph, %d mixed subjects (seed 3), MR priors, em_mr" % args.subjects, "steps": args.steps, "warmup": args.warmup,
         "impute_kernel_ms": statistics.median(a_ms), "em_kernel_ms": statistics.median(b_ms),
         "text_route_s": statistics.median(c_s) if c_s else None, "text_steps": args.text_steps,
+        "merge_ms": statistics.median(d_ms), "merge_records_ms": statistics.median(e_ms),
+        "merge_records_wall_ms": statistics.median(e_wall), "export_wall_ms": statistics.median(x_wall),
         "em_stats": stats, "entries": entries, "text_entries": sum(len(d) for d in counts.values()) if c_s else None,
     }))
 
