@@ -81,28 +81,25 @@ struct DevArgs {
   uint32_t ones_prior;    // index of the all-ones prior matrix (impute.py:1696-1700)
   const uint32_t *order;  // subject indices this launch works on
   uint32_t n_work;
-  uint32_t *queue;        // [0] general work counter [1] row head [2] plan-B list length [3] plan-B work counter
-                          // [4] one-wave kernel work counter [5] its hand-over count [6] heavy plan-B subjects
-                          // [7] its heavier hand-overs [8] pair pool head [9] / [10] work items of the one-wave /
-                          // bigger-item table kernels  (GRIM_NQ words; the rest is listed at GRIM_NQ)
+  uint32_t *queue;        // the u32 words of the run-state block: GRIM_Q_* below
   grim_subject_result *res;
   grim_row *rows;
-  uint32_t *row_head;
+  uint32_t *row_head;     // alias of queue + GRIM_Q_ROWS
   uint32_t row_cap;
   uint8_t *scratch;
   uint32_t *wctr;               // work counters of the table kernels, GRIM_NSLICE per kernel, a 128-byte line each (slice_next)
   SlotLayout lay;
   uint32_t pair_cap, tab_cap, bset_cap, proj_cap;
   uint32_t *small_ctr;           // half-wave kernel: per wave {probes, frequency vectors}, plain stores; summed on request
-  unsigned long long *counters;  // [0] probes [1] nbr ids [2] freq vectors [3] rows [4] overflow flag
+  unsigned long long *counters;  // the u64 words of the run-state block: GRIM_C_* below
   uint32_t *bail_list;           // subjects the one-wave kernel hands to the general kernel: light ones from the front
-                                 // (count queue[5]), heavier ones from the back (count queue[7]); n_medium entries
+                                 // (count GRIM_Q_BAIL), heavier ones from the back (count GRIM_Q_BAIL_HEAVY); n_medium entries
   uint32_t n_medium;
-  uint32_t *mid_list;            // subjects the mid-size kernel (grim_mid.h) hands to the general kernel (count queue[17]); null:
+  uint32_t *mid_list;            // subjects the mid-size kernel (grim_mid.h) hands to the general kernel (count GRIM_Q_MID); null:
                                  // that kernel is switched off and the general kernel takes its own list and the one-wave
                                  // kernel's hand-overs itself
   uint32_t *next_list;           // subjects handed to the next kernel (plan B): light ones from the front
-  uint32_t *next_count;          // (count queue[2]), heavy ones from the back (count queue[6]) -- heavy first
+  uint32_t *next_count;          // (count GRIM_Q_NEXT: alias of queue + GRIM_Q_NEXT), heavy ones from the back (count GRIM_Q_NEXT_HEAVY) -- heavy first
   uint32_t next_cap;             // entries in next_list
   uint32_t flags;                // diagnostic switches (environment, read when the batch is created): GRIM_F_*
   PairRec *ppool;                // accepted pairs of subjects whose tables the table kernels build (grim_tables.h)
@@ -124,13 +121,52 @@ struct DevArgs {
 };
 #define GRIM_F_NO_NODUP 2u       // DevArgs.flags (GRIM_NO_NODUP=1): the pair passes always run their dedup (test switch)
 #define GRIM_F_NO_SIDEMASK 4u    // (GRIM_NO_SIDEMASK=1): tiled passes dedup through the slot's hash table as before round 4 (test switch)
-#define GRIM_NQ 24               // u32 words of `queue` (the run state block is counters + queue):
-                                 // [13] bucket-start slots used [14] work units [15] units done by earlier launches of the run
-                                 // [16] work counter of the mid-size kernel [17] its hand-overs to the general kernel
-                                 // [18] lines the device tokenizer handed back (GRIM_Q_IRREGULAR, grim_tokdev.h); [11] [19] [20] free
-                                 // [12] items the workgroup split kernel took [21] the workgroup merge kernel [22] of those, with an
-                                 // overflowed bucket [23] their largest pair count  (diagnostics, GRIM_DEBUG_CLASSES=1)
-                                 // (the table kernels' own work counters are DevArgs.wctr)
+
+// ---- the run-state block: DevArgs.counters (GRIM_NCTR u64 words), then DevArgs.queue (GRIM_NQ u32 words) ---------------------
+// Every kernel of the run path talks to the host through it.  At the end of a stage grim_finish_kernel copies the whole block
+// to the batch's pinned host copy and, unless a second stage follows (stage2_pending: that stage works on the block as it
+// is and ends with a finish kernel of its own), resets every word to the value in the last column.  The table kernels' own work
+// counters are DevArgs.wctr, the half-wave kernel's statistics DevArgs.small_ctr.
+//   word                   what it holds: who writes it                              | who reads it                            | reset to
+enum {
+  GRIM_Q_GENERAL = 0,    // work counter of the general kernel: that kernel            | that kernel                             | 0
+  GRIM_Q_ROWS,           // row pool head (DevArgs.row_head): whoever takes rows       | host: rows_used, overflow test          | row_head0
+  GRIM_Q_NEXT,           // light subjects in next_list (DevArgs.next_count): push_next| Plan-B kernel, stage2_pending, host     | 0
+  GRIM_Q_PLANB_WORK,     // work counter of the Plan-B kernel: that kernel             | that kernel                             | 0
+  GRIM_Q_MEDIUM_WORK,    // work counter of the one-wave kernel: that kernel           | that kernel                             | 0
+  GRIM_Q_BAIL,           // light hand-overs in bail_list: one-wave kernel             | mid-size or general kernel, host debug  | 0
+  GRIM_Q_NEXT_HEAVY,     // heavy subjects at the back of next_list: push_next         | Plan-B kernel, stage2_pending, host     | 0
+  GRIM_Q_BAIL_HEAVY,     // heavier hand-overs at the back of bail_list: one-wave k.   | mid-size or general kernel, host debug  | 0
+  GRIM_Q_POOL,           // pair pool head: pool_take                                  | host: pool_asked (how far to grow)      | 0
+  GRIM_Q_T1,             // work items in t1_list: push_tab_work                       | one-wave table kernel, stage2_pending   | 0
+  GRIM_Q_T2,             // work items in t2_list: push_tab_work                       | bigger-item table kernels, stage2_pend. | 0
+  GRIM_Q_FREE11,         // free                                                       |                                         | 0
+  GRIM_Q_DBG_SPLIT_WG,   // items the workgroup split kernel took: that kernel         | host debug (GRIM_DEBUG_CLASSES=1)       | 0
+  GRIM_Q_TBOFF,          // bucket-start slots used (tboff): split kernels             | the same kernels (it is their head)     | 0
+  GRIM_Q_TUNITS,         // work units in tunits: split kernels                        | bucket kernel, host debug               | 0
+  GRIM_Q_TUNITS_DONE,    // first unit of the bucket kernel: nobody, it stays 0        | bucket kernel                           | 0
+  GRIM_Q_MID_WORK,       // work counter of the mid-size kernel: that kernel           | that kernel                             | 0
+  GRIM_Q_MID,            // hand-overs in mid_list: mid-size kernel                    | general kernel, host debug              | 0
+  GRIM_Q_IRREGULAR,      // lines the device tokenizer handed back: tokenizer kernel   | host: n_irregular                       | 0
+  GRIM_Q_FREE19,         // free                                                       |                                         | 0
+  GRIM_Q_FREE20,         // free                                                       |                                         | 0
+  GRIM_Q_DBG_MERGE_WG,   // items the workgroup merge kernel took: that kernel         | host debug                              | 0
+  GRIM_Q_DBG_MERGE_OVF,  // ... of those, with an overflowed bucket: that kernel       | host debug                              | 0
+  GRIM_Q_DBG_MERGE_MAX,  // ... their largest pair count: that kernel                  | host debug                              | 0
+};
+#define GRIM_NQ 24  // u32 words of `queue`
+static_assert(GRIM_Q_DBG_MERGE_MAX + 1 == GRIM_NQ && GRIM_NQ % 2 == 0, "every queue word has a name; they fill whole u64 words");
+enum {
+  GRIM_C_PROBES = 0,     // hash probes: general and mid-size kernel                   | host: grim_batch_counters               | 0
+  GRIM_C_NBR,            // neighbour ids read: the same                               | host: grim_batch_counters               | 0
+  GRIM_C_FREQ,           // frequency vectors read: the same                           | host: grim_batch_counters               | 0
+  GRIM_C_ROWS,           // rows: nobody (GRIM_Q_ROWS counts them)                     | nobody                                  | 0
+  GRIM_C_OVERFLOW,       // a pool was too small: run_overflow                         | host: the run fails with -2             | 0
+  // words 5..7 free.  Then GRIM_C_SLICES slices of GRIM_C_SLICE_WORDS words {probes, neighbour ids, frequency vectors, free}: a
+  // block of the one-wave kernel adds to the slice blockIdx.x picks, so that its waves do not queue on one address; the
+  // host folds the slices into its copy of words 0..2.  Reset to 0 like the rest.
+};
+enum { GRIM_C_SLICE0 = 8, GRIM_C_SLICES = 64, GRIM_C_SLICE_WORDS = 4 };
 
 #ifndef GRIM_HEAVY_LOCI
 #define GRIM_HEAVY_LOCI 3
@@ -139,21 +175,45 @@ struct DevArgs {
 // of thousands of pairs) go to the head of its queue so that they do not start last and become the tail.
 __device__ __forceinline__ void push_next(const DevArgs &A, uint32_t si, bool heavy) {
   if (heavy)
-    A.next_list[A.next_cap - 1u - atomicAdd(A.queue + 6, 1u)] = si;
+    A.next_list[A.next_cap - 1u - atomicAdd(A.queue + GRIM_Q_NEXT_HEAVY, 1u)] = si;
   else
     A.next_list[atomicAdd(A.next_count, 1u)] = si;
 }
 
+// a pool (rows, pair records, bucket starts, work units) was too small: the run reports it and the caller splits the
+// batch or grows the pool and runs again
+__device__ __forceinline__ void run_overflow(const DevArgs &A) { atomicExch(&A.counters[GRIM_C_OVERFLOW], 1ull); }
+
+// nU records of the pair pool for one subject's accepted pairs; GRIM_NONE: the pool is full.  One lane calls.
+__device__ __forceinline__ uint32_t pool_take(const DevArgs &A, uint32_t nU) {
+  const uint32_t off = atomicAdd(A.queue + GRIM_Q_POOL, nU);
+  if (off + nU <= A.ppool_cap) return off;
+  run_overflow(A);
+  return GRIM_NONE;
+}
+
+// the work item "build the tables of subject si from records [off, off + nU) of the pair pool", to the table kernels that
+// take items of its size.  One lane calls.
+__device__ __forceinline__ void push_tab_work(const DevArgs &A, uint32_t si, uint32_t nU, uint32_t off, uint32_t mask) {
+  const TabWork w = {si, nU, off, mask};
+  if (nU <= GRIM_TAB_T1_MAX)
+    A.t1_list[atomicAdd(A.queue + GRIM_Q_T1, 1u)] = w;
+  else
+    A.t2_list[atomicAdd(A.queue + GRIM_Q_T2, 1u)] = w;
+}
+
+// does a second stage follow: subjects waiting for Plan B/C, or accepted pairs waiting for the table kernels.  The finish
+// kernel (keep the block or reset it) and the host (launch the stage or not) decide by this one sum.
+__host__ __device__ __forceinline__ uint32_t stage2_pending(const uint32_t *q) {
+  return q[GRIM_Q_NEXT] + q[GRIM_Q_NEXT_HEAVY] + q[GRIM_Q_T1] + q[GRIM_Q_T2];
+}
+
 // ---- optional stage timers (diagnostic build only: hipcc -DGRIM_STAMPS; never in the shipped .so) ----
-#define GRIM_STAMP_BASE (8 + 4 * 64)
+#define GRIM_STAMP_BASE (GRIM_C_SLICE0 + GRIM_C_SLICE_WORDS * GRIM_C_SLICES)
 #ifdef GRIM_STAMPS
 #define GRIM_HIST_BASE (GRIM_STAMP_BASE + 16)  // diagnostic build: log2 histograms, 8 x 24 buckets
 #define GRIM_MID_BASE (GRIM_HIST_BASE + 192)   // ... and the mid-size kernel's stage timers [0..15], hand-over reasons [16..31]
-#define GRIM_NCTR (8 + 4 * 64 + 16 + 192 + 32)
-#else
-#define GRIM_NCTR (8 + 4 * 64 + 16)
-#endif
-#ifdef GRIM_STAMPS
+#define GRIM_NCTR (GRIM_MID_BASE + 32)
 #define STAMP_BEGIN() unsigned long long _t0 = wall_clock64()
 #define STAMP(k)                                                           \
   do {                                                                     \
@@ -174,11 +234,13 @@ __device__ __forceinline__ void push_next(const DevArgs &A, uint32_t si, bool he
   } while (0)
 #define STAMP_NOW() wall_clock64()
 #else
+#define GRIM_NCTR (GRIM_STAMP_BASE + 16)
 #define STAMP_BEGIN()
 #define STAMP(k)
 #define HIST(h, v, w)
 #define STAMP_NOW() 0ull
 #endif
+#define GRIM_STATE_WORDS (GRIM_NCTR + GRIM_NQ / 2)  // u64 words of the run-state block
 
 // ---- small helpers ------------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {

@@ -43,14 +43,14 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_WG_PER_CU) void grim_plan_a_kernel(De
   Slot S = make_slot(A, blockIdx.x);
   // hand-overs of the one-wave kernel (earlier in the stream): the heavier ones, at the back of its list, are
   // taken first, then this kernel's own subjects (heaviest first), then the light hand-overs
-  const uint32_t n_bail = A.bail_list ? A.queue[5] : 0, n_bail_heavy = A.bail_list ? A.queue[7] : 0;
+  const uint32_t n_bail = A.bail_list ? A.queue[GRIM_Q_BAIL] : 0, n_bail_heavy = A.bail_list ? A.queue[GRIM_Q_BAIL_HEAVY] : 0;
   // behind the mid-size kernel (grim_mid.h) this kernel only takes what that one handed over
-  const uint32_t n_mid = A.mid_list ? A.queue[17] : 0;
+  const uint32_t n_mid = A.mid_list ? A.queue[GRIM_Q_MID] : 0;
   if (tid < GRIM_NWAVE * 4) ((unsigned long long *)sh.wctr)[tid] = 0;
   wg_arena(sh, wt);
   __syncthreads();
   for (;;) {
-    if (tid == 0) sh.bc[3] = atomicAdd(A.queue, 1u);
+    if (tid == 0) sh.bc[3] = atomicAdd(A.queue + GRIM_Q_GENERAL, 1u);
     __syncthreads();
     const uint32_t w = sh.bc[3];
     if (A.mid_list ? w >= n_mid : w >= A.n_work + n_bail + n_bail_heavy) break;
@@ -159,9 +159,9 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_WG_PER_CU) void grim_plan_a_kernel(De
       c1 += sh.wctr[wv][1];
       c2 += sh.wctr[wv][2];
     }
-    atomicAdd(&A.counters[0], c0);
-    atomicAdd(&A.counters[1], c1);
-    atomicAdd(&A.counters[2], c2);
+    atomicAdd(&A.counters[GRIM_C_PROBES], c0);
+    atomicAdd(&A.counters[GRIM_C_NBR], c1);
+    atomicAdd(&A.counters[GRIM_C_FREQ], c2);
   }
 }
 
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64) void grim_small_compact_kernel(DevArgs A, const
   if (lane == 0) base = atomicAdd(A.row_head, total);
   base = __shfl(base, 0);
   if (base + total > stage_base) {  // the pool is full: reported like every other row overflow (the caller splits the batch)
-    if (lane == 0) atomicExch(&A.counters[4], 1ull);
+    if (lane == 0) run_overflow(A);
     return;
   }
   if (cnt == 0) return;
@@ -243,25 +243,17 @@ __global__ __launch_bounds__(256) void grim_export_kernel(uint4 *__restrict__ ds
   for (; i < n16; i += step) dst[i] = src[i];
 }
 
-// zero the counters and work heads of a batch (one launch instead of several memsets)
-__global__ void grim_reset_kernel(unsigned long long *counters, uint32_t *queue, uint32_t row_head0) {
-  for (int i = threadIdx.x; i < GRIM_NCTR; i += blockDim.x) counters[i] = 0;
-  if (threadIdx.x < GRIM_NQ) queue[threadIdx.x] = threadIdx.x == 1 ? row_head0 : 0u;
-}
-
-// End of a stage: the state block (counters, then the eight queue words) goes straight to the batch's pinned
-// host copy, and -- unless Plan B still has work queued, which needs the heads as they are -- the device copy is
-// zeroed for the next run.  One small kernel instead of a copy engine job now and a reset kernel next time.
+// End of a stage: the run-state block (the GRIM_NCTR counter words, then the GRIM_NQ queue words: grim_dev.h) goes straight
+// to the batch's pinned host copy, and -- unless a second stage follows (stage2_pending), which needs the heads as they
+// are -- the device copy is reset for the next run.  One small kernel instead of a copy engine job now and a reset launch next time.
 __global__ void grim_finish_kernel(unsigned long long *state, unsigned long long *host_state, uint32_t row_head0, int after_plan_b) {
   __shared__ uint32_t pending;
-  const uint32_t *queue = (const uint32_t *)(state + GRIM_NCTR);
-  // subjects waiting for Plan B/C, or accepted pairs waiting for the table kernels: a second stage follows
-  if (threadIdx.x == 0) pending = after_plan_b ? 0u : queue[2] + queue[6] + queue[9] + queue[10];
-  for (int i = threadIdx.x; i < GRIM_NCTR + GRIM_NQ / 2; i += blockDim.x) host_state[i] = state[i];
+  if (threadIdx.x == 0) pending = after_plan_b ? 0u : stage2_pending((const uint32_t *)(state + GRIM_NCTR));
+  for (int i = threadIdx.x; i < GRIM_STATE_WORDS; i += blockDim.x) host_state[i] = state[i];
   __syncthreads();
   if (pending) return;  // the second stage works on this state
   for (int i = threadIdx.x; i < GRIM_NCTR; i += blockDim.x) state[i] = 0;
-  if (threadIdx.x < GRIM_NQ) ((uint32_t *)(state + GRIM_NCTR))[threadIdx.x] = threadIdx.x == 1 ? row_head0 : 0u;
+  if (threadIdx.x < GRIM_NQ) ((uint32_t *)(state + GRIM_NCTR))[threadIdx.x] = threadIdx.x == GRIM_Q_ROWS ? row_head0 : 0u;
 }
 
 // =================================================================================================
@@ -392,7 +384,7 @@ struct grim_batch {
   uint32_t n_timed;
   uint32_t rows_used;
   bool ran_ok = false;  // the last grim_batch_run finished and nothing was loaded since: res / rows hold its results (grim_em_accumulate)
-  unsigned long long counters[8];
+  unsigned long long counters[GRIM_C_SLICE0];  // the last run's GRIM_C_* words, the slices folded in
 };
 
 static thread_local std::string g_err;
@@ -760,7 +752,7 @@ static bool batch_plan(grim_batch *b, const EnginePlan &pl) {
   const uint64_t n = pl.n_subj ? pl.n_subj : 1;
   uint64_t o = 0;
   auto take = [&](uint64_t bytes) { uint64_t r = o; o = align256(o + bytes); return r; };
-  const uint64_t o_state = take(8ull * (GRIM_NCTR + GRIM_NQ / 2));
+  const uint64_t o_state = take(8ull * GRIM_STATE_WORDS);
   // device tokenizer: line records and the chunk's text come first -- a run whose lines are all tokenised on the device
   // copies the arena only up to here
   const bool devtok = pl.text_cap != 0;
@@ -804,8 +796,8 @@ static bool batch_plan(grim_batch *b, const EnginePlan &pl) {
   DevArgs &A = b->a;
   A.counters = (unsigned long long *)(b->d_in + o_state);
   A.queue = (uint32_t *)(A.counters + GRIM_NCTR);
-  A.row_head = A.queue + 1;
-  A.next_count = A.queue + 2;
+  A.row_head = A.queue + GRIM_Q_ROWS;
+  A.next_count = A.queue + GRIM_Q_NEXT;
   A.subj = (const grim_subject *)(b->d_in + o_subj);
   b->d_small = (SmallRec *)(b->d_in + o_small);
   b->d_lines = devtok ? (LineRec *)(b->d_in + o_lines) : nullptr;
@@ -921,7 +913,7 @@ grim_batch *engine_batch_create(grim_ctx *c, const grim_graph *g, const grim_par
     memset((void *)b, 0, sizeof(*b));
     b->ctx = c;
     bool ok = true;
-    if (hipHostMalloc((void **)&b->hstate, 8 * (GRIM_NCTR + GRIM_NQ / 2)) != hipSuccess) {
+    if (hipHostMalloc((void **)&b->hstate, 8 * GRIM_STATE_WORDS) != hipSuccess) {
       b->hstate = nullptr;
       ok = false;
     }
@@ -1153,7 +1145,7 @@ int engine_batch_load(grim_batch *b, const EngineLoad *ld) {
   A.n_work = ld->n_general;
   // the run state travels with the input: clean counters and work heads, rows of the half-wave kernel's fixed region taken
   unsigned long long *hs = (unsigned long long *)b->h_in;
-  memset(hs, 0, 8 * (GRIM_NCTR + GRIM_NQ / 2));
+  memset(hs, 0, 8 * GRIM_STATE_WORDS);
   // (rows are bump-allocated from 0; the half-wave kernel's staging region is the top of the pool)
   {
     const uint64_t staged = ((uint64_t)b->n_small + b->n_dev_lines) * b->small_stride;
@@ -1529,6 +1521,9 @@ static int read_phase_times(grim_batch *b) {
   return 0;
 }
 
+// subjects the first stage left for the Plan-B kernel (q: the queue words of the run-state block)
+static inline uint32_t planb_count(const uint32_t *q) { return q[GRIM_Q_NEXT] + q[GRIM_Q_NEXT_HEAVY]; }
+
 int engine_batch_wait(grim_batch *b) {
   if (!b) return -1;
   grim_ctx *c = b->ctx;
@@ -1542,18 +1537,19 @@ int engine_batch_wait(grim_batch *b) {
   b->ran_ok = false;
   HIPCHK(hipEventSynchronize(b->ev_done), c, -1);
   if (read_phase_times(b) != 0) return -1;
-  uint32_t head[GRIM_NQ];
-  memcpy(head, b->hstate + GRIM_NCTR, 4 * GRIM_NQ);
+  uint32_t q[GRIM_NQ];  // the queue words as the last finish kernel left them in the pinned block
+  auto read_queue = [&] { memcpy(q, b->hstate + GRIM_NCTR, sizeof(q)); };
+  read_queue();
   // ---- stage 2: Plan B / C when the first stage left subjects for it, then the table kernels ONCE over the accepted
   // pairs both stages queued (a round after each stage cost their tails twice) -------------------------------------
-  const bool run_b = A.prm.planb && head[2] + head[6] > 0;
-  if (run_b || head[2] + head[6] + head[9] + head[10] > 0) {
+  const bool run_b = A.prm.planb && planb_count(q) > 0;
+  if (run_b || stage2_pending(q) > 0) {
     {
       std::lock_guard<std::mutex> lk(c->run_mu);
       if (bind_scratch(b) != 0) return -1;
       if (run_b) {
         // the plan-A kernels leave the list of subjects in next_list/next_count
-        uint32_t grid = b->n_slots < head[2] + head[6] ? b->n_slots : head[2] + head[6];
+        uint32_t grid = b->n_slots < planb_count(q) ? b->n_slots : planb_count(q);
         launch(b, PH_PLAN_B, grim_plan_b_kernel, dim3(grid), dim3(GRIM_WG), A);
         if (hipGetLastError() != hipSuccess) {
           set_err(c, "grim_batch_run: plan-B launch failed");
@@ -1567,7 +1563,7 @@ int engine_batch_wait(grim_batch *b) {
     }
     HIPCHK(hipEventSynchronize(b->ev_done), c, -1);
     if (read_phase_times(b) != 0) return -1;
-    memcpy(head, b->hstate + GRIM_NCTR, 4 * GRIM_NQ);
+    read_queue();
   }
   if (b->timing) {
     for (int p = 0; p < PH_COUNT; ++p) b->acc_ms[p] += b->ms[p];
@@ -1575,18 +1571,18 @@ int engine_batch_wait(grim_batch *b) {
   }
   static const int dbg_classes = env_int("GRIM_DEBUG_CLASSES", 0);
   if (dbg_classes)
-    fprintf(stderr, "grim classes: mid-size kernel took %u, handed %u to the general kernel\n", head[16], head[17]);
-  if (dbg_classes)
-    fprintf(stderr, "grim classes: small %u medium %u general %u | medium->general %u (+%u heavier), to plan B %u (+%u heavy) | table items %u one-wave, %u bigger (%u work units), %u pair records; workgroup merge: %u items (%u with an overflowed bucket), up to %u pairs; workgroup split: %u items | stage 1 %s\n",
-            b->n_small, b->n_medium, b->n_general, head[5], head[7], head[2], head[6], head[9], head[10], head[14], head[8], head[21], head[22], head[23], head[12],
+    fprintf(stderr, "grim classes: mid-size kernel took %u, handed %u to the general kernel\n"
+            "grim classes: small %u medium %u general %u | medium->general %u (+%u heavier), to plan B %u (+%u heavy) | table items %u one-wave, %u bigger (%u work units), %u pair records; workgroup merge: %u items (%u with an overflowed bucket), up to %u pairs; workgroup split: %u items | stage 1 %s\n",
+            q[GRIM_Q_MID_WORK], q[GRIM_Q_MID], b->n_small, b->n_medium, b->n_general, q[GRIM_Q_BAIL], q[GRIM_Q_BAIL_HEAVY], q[GRIM_Q_NEXT], q[GRIM_Q_NEXT_HEAVY], q[GRIM_Q_T1], q[GRIM_Q_T2],
+            q[GRIM_Q_TUNITS], q[GRIM_Q_POOL], q[GRIM_Q_DBG_MERGE_WG], q[GRIM_Q_DBG_MERGE_OVF], q[GRIM_Q_DBG_MERGE_MAX], q[GRIM_Q_DBG_SPLIT_WG],
             b->graph_state == 1 ? "replayed as a hipGraph" : "launched directly");
-  memcpy(b->counters, b->hstate, 64);
+  memcpy(b->counters, b->hstate, sizeof(b->counters));
   b->small_ctr_pending = b->n_small + b->n_dev_lines > 0;
-  for (int sh = 0; sh < 64; ++sh)
-    for (int k = 0; k < 3; ++k) b->counters[k] += b->hstate[8 + 4 * sh + k];
-  b->rows_used = head[1];
-  b->pool_asked = head[8];
-  b->n_irregular = head[GRIM_Q_IRREGULAR];
+  for (int sh = 0; sh < GRIM_C_SLICES; ++sh)  // a slice: {probes, neighbour ids, frequency vectors, free}
+    for (int k = GRIM_C_PROBES; k <= GRIM_C_FREQ; ++k) b->counters[k] += b->hstate[GRIM_C_SLICE0 + GRIM_C_SLICE_WORDS * sh + k];
+  b->rows_used = q[GRIM_Q_ROWS];
+  b->pool_asked = q[GRIM_Q_POOL];
+  b->n_irregular = q[GRIM_Q_IRREGULAR];
 #ifdef GRIM_STAMPS
   fprintf(stderr, "grim stamps (us):");
   for (int k = 0; k < 16; ++k) fprintf(stderr, " [%d]%.0f", k, b->hstate[GRIM_STAMP_BASE + k] / 100.0);
@@ -1605,7 +1601,7 @@ int engine_batch_wait(grim_batch *b) {
     fprintf(stderr, "\n");
   }
 #endif
-  if (b->counters[4] != 0 || head[1] > A.row_cap) {
+  if (b->counters[GRIM_C_OVERFLOW] != 0 || q[GRIM_Q_ROWS] > A.row_cap) {
     if (b->rows_used > A.row_cap) b->rows_used = A.row_cap;
     set_err(c, "grim_batch_run: output row pool exhausted (raise GRIM_ROW_CAP or lower the batch size)");
     return -2;
@@ -1658,14 +1654,12 @@ extern "C" int grim_batch_counters(const grim_batch *cb, uint64_t out[4]) {
     std::vector<uint32_t> h(2 * (size_t)b->n_small_waves);
     HIPCHK(hipMemcpy(h.data(), b->a.small_ctr, 4 * h.size(), hipMemcpyDeviceToHost), c, -1);
     for (size_t i = 0; i < h.size(); i += 2) {
-      b->counters[0] += h[i];
-      b->counters[2] += h[i + 1];
+      b->counters[GRIM_C_PROBES] += h[i];
+      b->counters[GRIM_C_FREQ] += h[i + 1];
     }
     b->small_ctr_pending = false;
   }
-  out[0] = b->counters[0];
-  out[1] = b->counters[1];
-  out[2] = b->counters[2];
+  for (int k = GRIM_C_PROBES; k <= GRIM_C_FREQ; ++k) out[k] = b->counters[k];
   out[3] = b->rows_used;
   return 0;
 }

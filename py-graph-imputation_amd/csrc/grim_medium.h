@@ -346,13 +346,7 @@ __device__ inline int medium_subject(const DevArgs &A, WaveMed &M, uint32_t si, 
       // more pairs than the one-wave shuffle code holds: the tables are the table kernels' work (grim_tables.h).  The
       // accepted pairs become records of the batch's pair pool, in sequence order, and a work item.
       uint32_t off = 0;
-      if (lane == 0) {
-        off = atomicAdd(A.queue + 8, nU);
-        if (off + nU > A.ppool_cap) {
-          atomicExch(&A.counters[4], 1ull);
-          off = GRIM_NONE;
-        }
-      }
+      if (lane == 0) off = pool_take(A, nU);
       off = __shfl(off, 0);
       if (off != GRIM_NONE) {
         for (uint32_t u = lane; u < nU; u += 64) {
@@ -365,17 +359,7 @@ __device__ inline int medium_subject(const DevArgs &A, WaveMed &M, uint32_t si, 
           r.e2 = pr.e2;
           A.ppool[off + u] = r;
         }
-        if (lane == 0) {
-          TabWork w;
-          w.si = si;
-          w.n = nU;
-          w.off = off;
-          w.mask = 3;
-          if (nU <= GRIM_TAB_T1_MAX)
-            A.t1_list[atomicAdd(A.queue + 9, 1u)] = w;
-          else
-            A.t2_list[atomicAdd(A.queue + 10, 1u)] = w;
-        }
+        if (lane == 0) push_tab_work(A, si, nU, off, 3);
       }
       grim_subject_result out;
       memset(&out, 0, sizeof(out));
@@ -434,7 +418,7 @@ __global__ __launch_bounds__(64) void grim_plan_a_medium_kernel(DevArgs A, const
   RowBlock rb = {0, 0, GRIM_ROW_GRAB};
   for (;;) {
     uint32_t w0 = 0;
-    if (lane_id() == 0) w0 = atomicAdd(A.queue + 4, CH);
+    if (lane_id() == 0) w0 = atomicAdd(A.queue + GRIM_Q_MEDIUM_WORK, CH);
     w0 = __shfl(w0, 0);
     if (w0 >= n) break;
     const uint32_t w1 = w0 + CH < n ? w0 + CH : n;
@@ -444,17 +428,17 @@ __global__ __launch_bounds__(64) void grim_plan_a_medium_kernel(DevArgs A, const
       if (rc != 0 && lane_id() == 0) {
         // the heavier hand-overs from the back of the list: the general kernel takes them first
         if (rc == 2)
-          bail_list[n - 1u - atomicAdd(A.queue + 7, 1u)] = si;
+          bail_list[n - 1u - atomicAdd(A.queue + GRIM_Q_BAIL_HEAVY, 1u)] = si;
         else
-          bail_list[atomicAdd(A.queue + 5, 1u)] = si;
+          bail_list[atomicAdd(A.queue + GRIM_Q_BAIL, 1u)] = si;
       }
       WAVE_SYNC();
     }
   }
   if (lane_id() == 0) {
-    unsigned long long *c = A.counters + 8 + 4 * (blockIdx.x & 63);
-    atomicAdd(&c[0], acc[0]);
-    atomicAdd(&c[1], acc[1]);
-    atomicAdd(&c[2], acc[2]);
+    unsigned long long *c = A.counters + GRIM_C_SLICE0 + GRIM_C_SLICE_WORDS * (blockIdx.x & (GRIM_C_SLICES - 1));
+    atomicAdd(&c[GRIM_C_PROBES], acc[0]);  // a slice's words are in the order of words 0..2
+    atomicAdd(&c[GRIM_C_NBR], acc[1]);
+    atomicAdd(&c[GRIM_C_FREQ], acc[2]);
   }
 }

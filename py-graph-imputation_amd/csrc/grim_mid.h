@@ -795,15 +795,7 @@ __device__ inline int mid_subject(const DevArgs &A, MidShared &M, uint32_t si) {
         at += (uint32_t)__popcll(V.bm[w]);
       }
       if (tid == 0) {
-        uint32_t off = 0;
-        if (nU > 64) {
-          off = atomicAdd(A.queue + 8, nU);
-          if (off + nU > A.ppool_cap) {
-            atomicExch(&A.counters[4], 1ull);  // the run reports the overflow; the caller grows the pool and runs again
-            off = GRIM_NONE;
-          }
-        }
-        M.bc[4] = off;
+        M.bc[4] = nU > 64 ? pool_take(A, nU) : 0u;
         M.out.n_pairs = nU;
         M.out.max_prob = mx;
       }
@@ -854,15 +846,13 @@ __device__ inline int mid_subject(const DevArgs &A, MidShared &M, uint32_t si) {
         emit_small_core(A, nU, e1, e2, prob, k1, k2, M.out, rb, 3);
       }
     } else if (off != GRIM_NONE && tid == 0) {
-      TabWork w;
-      w.si = si;
-      w.n = nU;
-      w.off = off;
-      w.mask = 3;
+      // push_tab_work's lines, written out: through the helper the compiler folds the two pushes of THIS kernel into one with
+      // a selected address (shorter by 88 bytes, but not the code that was measured; profiles/run_state_notes.md)
+      const TabWork w = {si, nU, off, 3};
       if (nU <= GRIM_TAB_T1_MAX)
-        A.t1_list[atomicAdd(A.queue + 9, 1u)] = w;
+        A.t1_list[atomicAdd(A.queue + GRIM_Q_T1, 1u)] = w;
       else
-        A.t2_list[atomicAdd(A.queue + 10, 1u)] = w;
+        A.t2_list[atomicAdd(A.queue + GRIM_Q_T2, 1u)] = w;
     }
     status = GRIM_ST_OK;
   } else if (A.prm.planb) {
@@ -891,11 +881,11 @@ __device__ inline int mid_subject(const DevArgs &A, MidShared &M, uint32_t si) {
 __global__ __launch_bounds__(GRIM_WG, GRIM_MID_WG_PER_CU) void grim_plan_a_mid_kernel(DevArgs A) {
   __shared__ MidShared M;
   const int tid = threadIdx.x;
-  const uint32_t n_bail = A.bail_list ? A.queue[5] : 0, n_bail_heavy = A.bail_list ? A.queue[7] : 0;
+  const uint32_t n_bail = A.bail_list ? A.queue[GRIM_Q_BAIL] : 0, n_bail_heavy = A.bail_list ? A.queue[GRIM_Q_BAIL_HEAVY] : 0;
   if (tid < 4) M.wctr[tid] = 0;
   __syncthreads();
   for (;;) {
-    if (tid == 0) M.bc[7] = atomicAdd(A.queue + 16, 1u);
+    if (tid == 0) M.bc[7] = atomicAdd(A.queue + GRIM_Q_MID_WORK, 1u);
     __syncthreads();
     const uint32_t w = M.bc[7];
     __syncthreads();
@@ -908,12 +898,12 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_MID_WG_PER_CU) void grim_plan_a_mid_k
     else
       si = A.bail_list[w - n_bail_heavy - A.n_work];
     const int rc = mid_subject(A, M, si);
-    if (rc != 0 && tid == 0) A.mid_list[atomicAdd(A.queue + 17, 1u)] = si;
+    if (rc != 0 && tid == 0) A.mid_list[atomicAdd(A.queue + GRIM_Q_MID, 1u)] = si;
     __syncthreads();
   }
   if (tid == 0) {
-    atomicAdd(&A.counters[0], M.wctr[0]);
-    atomicAdd(&A.counters[1], M.wctr[1]);
-    atomicAdd(&A.counters[2], M.wctr[2]);
+    atomicAdd(&A.counters[GRIM_C_PROBES], M.wctr[0]);
+    atomicAdd(&A.counters[GRIM_C_NBR], M.wctr[1]);
+    atomicAdd(&A.counters[GRIM_C_FREQ], M.wctr[2]);
   }
 }

@@ -1024,7 +1024,7 @@ __device__ __forceinline__ uint32_t wave_alloc_rows(const DevArgs &A, RowBlock &
   if (lane_id() == 0) {
     off = atomicAdd(A.row_head, take);
     if (off + take > A.row_cap) {
-      atomicExch(&A.counters[4], 1ull);
+      run_overflow(A);
       off = GRIM_NONE;
     }
   }
@@ -1154,14 +1154,7 @@ __device__ inline void emit_small(const DevArgs &A, WgShared &sh, const Slot &S,
 // build.  All threads call.
 __device__ inline void queue_tables(const DevArgs &A, WgShared &sh, const Slot &S, uint32_t nU, uint32_t si, uint32_t mask) {
   const int tid = threadIdx.x;
-  if (tid == 0) {
-    uint32_t off = atomicAdd(A.queue + 8, nU);
-    if (off + nU > A.ppool_cap) {
-      atomicExch(&A.counters[4], 1ull);  // the run reports the overflow; the caller splits the batch and runs it again
-      off = GRIM_NONE;
-    }
-    sh.bc[1] = off;
-  }
+  if (tid == 0) sh.bc[1] = pool_take(A, nU);
   __syncthreads();
   const uint32_t off = sh.bc[1];
   __syncthreads();
@@ -1176,17 +1169,7 @@ __device__ inline void queue_tables(const DevArgs &A, WgShared &sh, const Slot &
     r.e2 = pr.e2;
     A.ppool[off + u] = r;
   }
-  if (tid == 0) {
-    TabWork w;
-    w.si = si;
-    w.n = nU;
-    w.off = off;
-    w.mask = mask;
-    if (nU <= GRIM_TAB_T1_MAX)
-      A.t1_list[atomicAdd(A.queue + 9, 1u)] = w;
-    else
-      A.t2_list[atomicAdd(A.queue + 10, 1u)] = w;
-  }
+  if (tid == 0) push_tab_work(A, si, nU, off, mask);
   __syncthreads();
 }
 

@@ -985,12 +985,12 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_PLANB_WG_PER_CU) void grim_plan_b_ker
   __shared__ PbState st;
   const int tid = threadIdx.x;
   const int P = A.g.P;
-  const uint32_t n_heavy = A.queue[6], n_work = *A.next_count + n_heavy;
+  const uint32_t n_heavy = A.queue[GRIM_Q_NEXT_HEAVY], n_work = *A.next_count + n_heavy;
   Slot S = make_slot(A, blockIdx.x);
   wg_arena(sh, wt);  // the pair-stage work areas: free whenever pairs are scored, every pass has finished its sides by then
   __syncthreads();
   for (;;) {
-    if (tid == 0) sh.bc[3] = atomicAdd(A.queue + 3, 1u);  // own counter: no reset between kernels
+    if (tid == 0) sh.bc[3] = atomicAdd(A.queue + GRIM_Q_PLANB_WORK, 1u);  // own counter: no reset between kernels
     __syncthreads();
     const uint32_t w = sh.bc[3];
     if (w >= n_work) break;

@@ -364,7 +364,7 @@ __device__ inline void tables_wave(const DevArgs &A, WaveTabT1 &W, const TabWork
 // one wave = one work item at a time; waves are independent (no __syncthreads)
 __global__ __launch_bounds__(64) void grim_tables_wave_kernel(DevArgs A) {
   __shared__ WaveTabT1 W;
-  const uint32_t n_items = A.queue[9];  // written by the kernels before this one in the stream
+  const uint32_t n_items = A.queue[GRIM_Q_T1];  // written by the kernels before this one in the stream
   RowBlock rb = {0, 0, GRIM_ROW_GRAB};
   // one item per visit to the (sliced) work counters: the tail stays one item long
   SliceWalk sw = {blockIdx.x % GRIM_NSLICE, 0};
@@ -382,7 +382,7 @@ __device__ inline uint32_t tab_alloc_rows(const DevArgs &A, SH &sh, uint32_t n) 
   if (threadIdx.x == 0) {
     uint32_t off = n ? atomicAdd(A.row_head, n) : 0;
     if (n && off + n > A.row_cap) {
-      atomicExch(&A.counters[4], 1ull);
+      run_overflow(A);
       off = GRIM_NONE;
     }
     sh.bc[1] = off;
@@ -916,9 +916,9 @@ __device__ inline void tab_split_table(const DevArgs &A, TabShared &sh, const Sl
     __syncthreads();
   }
   if (tid == 0) {
-    uint32_t base = atomicAdd(A.queue + 13, nb + 1), ubase = atomicAdd(A.queue + 14, nb);
+    uint32_t base = atomicAdd(A.queue + GRIM_Q_TBOFF, nb + 1), ubase = atomicAdd(A.queue + GRIM_Q_TUNITS, nb);
     if (base + nb + 1 > A.tboff_cap || ubase + nb > A.tunits_cap) {
-      atomicExch(&A.counters[4], 1ull);  // reported like a row-pool overflow: the caller splits the batch
+      run_overflow(A);  // reported like a row-pool overflow: the caller splits the batch
       base = ubase = GRIM_NONE;
     }
     sh.bc[4] = base;
@@ -1019,9 +1019,9 @@ __device__ inline void tab_split_pops(const DevArgs &A, TabShared &sh, const Slo
   uint32_t *cnt = ncell <= TAB_MAXB ? sh.bcnt : S.gstart;  // cell starts: LDS unless there are more cells than it holds
   for (int c = tid; c <= ncell; c += GRIM_WG) cnt[c] = 0;
   if (tid == 0) {
-    uint32_t base = atomicAdd(A.queue + 13, (uint32_t)ncell + 1);
+    uint32_t base = atomicAdd(A.queue + GRIM_Q_TBOFF, (uint32_t)ncell + 1);
     if (base + ncell + 1 > A.tboff_cap) {
-      atomicExch(&A.counters[4], 1ull);
+      run_overflow(A);
       base = GRIM_NONE;
     }
     sh.bc[4] = base;
@@ -1178,7 +1178,7 @@ __device__ inline void tab_split_pops(const DevArgs &A, TabShared &sh, const Slo
     cr.pad = 0;
     A.tcell[base + c] = cr;
     if (cnt[c + 1] > cnt[c]) {  // a work unit per non-empty cell
-      const uint32_t k = atomicAdd(A.queue + 14, 1u);
+      const uint32_t k = atomicAdd(A.queue + GRIM_Q_TUNITS, 1u);
       if (k < A.tunits_cap) {
         TabUnit un;
         un.item = item;
@@ -1189,7 +1189,7 @@ __device__ inline void tab_split_pops(const DevArgs &A, TabShared &sh, const Slo
         un.pad[0] = un.pad[1] = un.pad[2] = 0;
         A.tunits[k] = un;
       } else {
-        atomicExch(&A.counters[4], 1ull);
+        run_overflow(A);
       }
     }
   }
@@ -1333,10 +1333,10 @@ __device__ inline void split_wave(const DevArgs &A, SplitWave &W, const TabWork 
   const uint32_t need_off = ncell + 1 + nb_all + n_tab, need_units = nb_all + (uint32_t)__popcll(cell_m);
   uint32_t base = 0, ubase = 0;
   if (lane == 0) {
-    base = atomicAdd(A.queue + 13, need_off);
-    ubase = atomicAdd(A.queue + 14, need_units);
+    base = atomicAdd(A.queue + GRIM_Q_TBOFF, need_off);
+    ubase = atomicAdd(A.queue + GRIM_Q_TUNITS, need_units);
     if (base + need_off > A.tboff_cap || ubase + need_units > A.tunits_cap) {
-      atomicExch(&A.counters[4], 1ull);  // reported like a row-pool overflow: the caller splits the batch
+      run_overflow(A);  // reported like a row-pool overflow: the caller splits the batch
       base = GRIM_NONE;
     }
     x.cell_base = base;
@@ -1458,7 +1458,7 @@ __device__ inline void split_wave(const DevArgs &A, SplitWave &W, const TabWork 
 
 __global__ __launch_bounds__(64) void grim_tables_split_wave_kernel(DevArgs A) {
   __shared__ SplitWave W;
-  const uint32_t n_items = A.queue[10];
+  const uint32_t n_items = A.queue[GRIM_Q_T2];
   SliceWalk sw = {blockIdx.x % GRIM_NSLICE, 0};
   for (;;) {
     const uint32_t item = slice_next(A.wctr, GRIM_WL_SPLIT_WAVE, n_items, sw);
@@ -1599,7 +1599,7 @@ __device__ inline void merge_wave(const DevArgs &A, const TabWork &w, const TabA
 }
 
 __global__ __launch_bounds__(64) void grim_tables_merge_wave_kernel(DevArgs A) {
-  const uint32_t n_items = A.queue[10];
+  const uint32_t n_items = A.queue[GRIM_Q_T2];
   RowBlock rb = {0, 0, GRIM_ROW_GRAB};
   SliceWalk sw = {blockIdx.x % GRIM_NSLICE, 0};
   for (;;) {
@@ -1623,7 +1623,7 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_TAB_WG_PER_CU) void grim_tables_split
   __shared__ TabShared sh;
   __shared__ SplitArena arena;
   const int tid = threadIdx.x;
-  const uint32_t n_items = A.queue[10];
+  const uint32_t n_items = A.queue[GRIM_Q_T2];
   Slot S = make_slot(A, blockIdx.x);
   if (tid == 0) {
     sh.hist = arena.a.hist;
@@ -1648,7 +1648,7 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_TAB_WG_PER_CU) void grim_tables_split
     if (tw_split_item(A, w)) continue;  // grim_tables_split_wave_kernel's
     const unsigned long long t_item = STAMP_NOW();
     (void)t_item;
-    if (tid == 0) atomicAdd(A.queue + 12, 1u);  // (GRIM_DEBUG_CLASSES=1 prints it)
+    if (tid == 0) atomicAdd(A.queue + GRIM_Q_DBG_SPLIT_WG, 1u);  // (GRIM_DEBUG_CLASSES=1 prints it)
     const bool hbm_way = (A.flags & GRIM_F_TABLES_HBM) != 0;
     const bool split0 = (w.mask & 1u) && !hbm_way;
     const bool split1 = ((w.mask >> 1) & 1u) && A.prm.out_haps && !(A.prm.em_mr || A.g.P == 1) && !hbm_way;
@@ -1675,10 +1675,10 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_TAB_WG_PER_CU) void grim_tables_split
 
 // second kernel: one wave = one work unit at a time.  The units are dealt to the waves round robin: a shared work
 // counter is ONE address, and an atomic on it costs ~12 ns whoever issues it -- 800 000 units would spend 5 ms there.
-// queue[15] = units done by earlier launches of the run (the finish kernel moves it up).
+// GRIM_Q_TUNITS_DONE = the first unit of this launch: 0, since the table kernels run once a run.
 __global__ __launch_bounds__(64) void grim_tables_bucket_kernel(DevArgs A) {
   __shared__ WaveTab<TAB_NB> W;
-  const uint32_t n_units = A.queue[14] < A.tunits_cap ? A.queue[14] : A.tunits_cap;
+  const uint32_t n_units = A.queue[GRIM_Q_TUNITS] < A.tunits_cap ? A.queue[GRIM_Q_TUNITS] : A.tunits_cap;
   const int lane = lane_id();
   const int P = A.g.P;
   constexpr uint32_t UM = (1u << TAB_SH) - 1u;
@@ -1693,7 +1693,7 @@ __global__ __launch_bounds__(64) void grim_tables_bucket_kernel(DevArgs A) {
   // pair numbers of unit i+2 and the header of unit i+3 are on their way, and the groups of unit i-1 are written -- its
   // place in the table's group list (an atomic on the item's counter) was asked for a unit ago.
   constexpr int NC = TAB_NB / 64;
-  const uint32_t k0 = A.queue[15] + vid;
+  const uint32_t k0 = A.queue[GRIM_Q_TUNITS_DONE] + vid;
   auto load_hdr = [&](uint32_t kk, TabUnit &u) {
     u.item = 0; u.tb = 0; u.off = 0; u.lo = 0; u.n = 0;
     if (kk < n_units) u = A.tunits[kk];
@@ -2015,7 +2015,7 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_TAB_WG_PER_CU) void grim_tables_merge
   __shared__ TabShared sh;
   __shared__ WgArena arena;
   const int tid = threadIdx.x;
-  const uint32_t n_items = A.queue[10];
+  const uint32_t n_items = A.queue[GRIM_Q_T2];
   Slot S = make_slot(A, blockIdx.x);
   if (tid == 0) {
     sh.hist = arena.hist;
@@ -2041,9 +2041,9 @@ __global__ __launch_bounds__(GRIM_WG, GRIM_TAB_WG_PER_CU) void grim_tables_merge
     const unsigned long long t_item = STAMP_NOW();
     (void)t_item;
     if (tid == 0) {  // (GRIM_DEBUG_CLASSES=1 prints these)
-      atomicAdd(A.queue + 21, 1u);
-      if (x.overflow[0] | x.overflow[1]) atomicAdd(A.queue + 22, 1u);
-      atomicMax(A.queue + 23, w.n);
+      atomicAdd(A.queue + GRIM_Q_DBG_MERGE_WG, 1u);
+      if (x.overflow[0] | x.overflow[1]) atomicAdd(A.queue + GRIM_Q_DBG_MERGE_OVF, 1u);
+      atomicMax(A.queue + GRIM_Q_DBG_MERGE_MAX, w.n);
     }
     const PairRec *rec = A.ppool + w.off;
     const uint32_t nU = w.n;

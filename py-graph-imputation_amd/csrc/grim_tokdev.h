@@ -27,7 +27,7 @@ struct DevTok {
   uint32_t graph_loci;
 };
 #define GRIM_REASON_HOST_TOKENIZER 7  // grim_subject_result.reason of a line the device tokenizer hands back to the host
-#define GRIM_Q_IRREGULAR 18           // queue word: lines handed back
+                                      // (counted in the queue word GRIM_Q_IRREGULAR)
 
 #define TOK_LANES (2 * GRIM_MAXL)
 #define TOK_LINES_PER_WAVE (64 / TOK_LANES)
