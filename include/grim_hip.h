@@ -399,6 +399,15 @@ const char *grim_stream_error(const grim_stream *s);
 /* in-memory texts after grim_stream_finish (which: 0..5 as grim_format, 6 = log) */
 const char *grim_stream_text(grim_stream *s, int which, uint64_t *len);
 int grim_stream_get_stats(const grim_stream *s, grim_stream_stats *out);
+/* The device tokenizer's verdicts so far (complete after grim_stream_finish).  *offered: lines the host's line splitter
+ * left to it -- a GL field of 1..144 bytes without '/', on a stream that has the device tokenizer on -- the sum of the
+ * chunks' counts.  *handed_back: those of them it flagged and the host's tokenizer took in the fix-up pass.  Either way
+ * the output is the same; the difference is a second pass.  Either pointer may be NULL.  0 or -1 (s is NULL). */
+int grim_stream_devtok_lines(const grim_stream *s, uint64_t *offered, uint64_t *handed_back);
+/* The hash the device dictionary tables are built and probed with: the name packed big-endian into six words, zero
+ * padded, then hashed with its length; a name's home slot in a locus's table is hash & (capacity - 1), capacity the
+ * smallest power of two >= max(16, 4 * alleles of the locus).  Host code, no GPU needed.  len <= 24, else 0. */
+uint32_t grim_tokname_hash(const char *name, uint32_t len);
 /* subjects the device could not resolve (GRIM_ST_UNSUPPORTED / GRIM_K_UNSUPPORTED): global line index, reason, id */
 uint64_t grim_stream_n_unsupported(const grim_stream *s);
 int grim_stream_unsupported(const grim_stream *s, uint64_t k, uint64_t *line, uint32_t *reason, const char **id, uint32_t *id_len);

@@ -813,7 +813,9 @@ static bool batch_plan(grim_batch *b, const EnginePlan &pl) {
   A.bail_list = (uint32_t *)(b->d_work + w_bail);
   A.next_list = (uint32_t *)(b->d_work + w_next);
   {
-    static const int no_mid = env_int("GRIM_NO_MID", 0);  // test switch: everything the mid-size kernel takes goes to the general kernel
+    // test switch: everything the mid-size kernel takes goes to the general kernel.  Read at every layout, like the other
+    // switches: a process that runs with it on and off (the tests do) must get what it asked for each time.
+    const int no_mid = env_int("GRIM_NO_MID", 0);
     A.mid_list = no_mid ? nullptr : (uint32_t *)(b->d_work + w_mid);
   }
   A.small_ctr = (uint32_t *)(b->d_work + w_ctr);
@@ -979,6 +981,13 @@ struct grim_devdict {
 static void pack_name(const char *p, size_t n, uint32_t (&w)[6]) {
   for (int i = 0; i < 6; ++i) w[i] = 0;
   for (size_t k = 0; k < n && k < GRIM_TOKNAME; ++k) w[k >> 2] |= (uint32_t)(uint8_t)p[k] << (24 - 8 * (k & 3));
+}
+
+extern "C" uint32_t grim_tokname_hash(const char *name, uint32_t len) {
+  if (!name || len > GRIM_TOKNAME) return 0;
+  uint32_t w[6];
+  pack_name(name, len, w);
+  return tokname_hash(w, len);
 }
 
 grim_devdict *engine_devdict_create(grim_ctx *c, const DictSnap *snap) {

@@ -297,6 +297,7 @@ struct grim_stream {
   grim_stream_stats st;
   std::atomic<uint64_t> tok_ns{0}, fmt_ns{0}, wr_ns{0};
   std::atomic<uint64_t> handed_back{0};  // lines the device tokenizer gave back to the host's
+  std::atomic<uint64_t> offered{0};      // lines the host left to the device tokenizer (the chunks' n_devtok)
 
   void fail(const std::string &m) {  // mu held
     if (!failed) {
@@ -346,6 +347,7 @@ static void assemble(grim_stream *s, Chunk *c) {
     c->n_devtok += T.n_devtok;
     race_overflow = race_overflow || T.race_overflow;
   }
+  s->offered += c->n_devtok;
   if (s->opt.want_records) {
     c->kinds.clear();
     for (uint32_t r = 0; r < c->n_ranges; ++r) c->kinds.insert(c->kinds.end(), c->tr[r].kind.begin(), c->tr[r].kind.end());
@@ -1628,6 +1630,13 @@ extern "C" int grim_stream_get_stats(const grim_stream *s, grim_stream_stats *ou
   out->unsupported = s->unsupported.size();
   out->bytes_h2d = engine_bytes_moved(nullptr, 0);
   out->bytes_d2h = engine_bytes_moved(nullptr, 1);
+  return 0;
+}
+
+extern "C" int grim_stream_devtok_lines(const grim_stream *s, uint64_t *offered, uint64_t *handed_back) {
+  if (!s) return -1;
+  if (offered) *offered = s->offered.load();
+  if (handed_back) *handed_back = s->handed_back.load();
   return 0;
 }
 

@@ -826,6 +826,7 @@ EXPORTS += [
     "grim_stream_error", "grim_stream_text", "grim_stream_get_stats", "grim_stream_n_unsupported", "grim_stream_unsupported",
     "grim_stream_next_records", "grim_stream_release_records", "grim_stream_free", "grim_stream_write_text",
     "grim_stream_segment", "grim_stream_n_segments", "grim_stream_segment_end", "grim_stream_segment_wait", "grim_stream_segment_place", "grim_default_threads", "grim_chunk_offsets", "grim_free",
+    "grim_stream_devtok_lines", "grim_tokname_hash",
 ]
 
 
@@ -960,12 +961,22 @@ def host_lib():
     L.grim_stream_segment_wait.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.grim_stream_segment_place.restype = C.c_int
     L.grim_stream_segment_place.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.grim_stream_devtok_lines.restype = C.c_int
+    L.grim_stream_devtok_lines.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.grim_tokname_hash.restype = C.c_uint32
+    L.grim_tokname_hash.argtypes = [C.c_char_p, C.c_uint32]
     L.grim_default_threads.restype = C.c_uint32
     L.grim_chunk_offsets.restype = C.c_int64
     L.grim_chunk_offsets.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.POINTER(C.c_uint64))]
     L.grim_free.argtypes = [C.c_void_p]
     _host_ready = True
     return L
+
+
+def tokname_hash(name):
+    """grim_tokname_hash of an allele name (bytes or str, at most 24 bytes)"""
+    b = name.encode() if isinstance(name, str) else bytes(name)
+    return int(host_lib().grim_tokname_hash(b, len(b)))
 
 
 def host_threads():
@@ -1319,6 +1330,12 @@ class Stream:
         st = StreamStats()
         host_lib().grim_stream_get_stats(self.h, C.byref(st))
         return st
+
+    def devtok_lines(self):
+        """-> (offered, handed_back): lines left to the device tokenizer, and those of them it gave back to the host's"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(host_lib().grim_stream_devtok_lines(self.h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
 
     def unsupported(self):
         L = host_lib()

@@ -543,6 +543,7 @@ class Imputation(object):
                 "counters": [int(x) for x in stats.counters],
                 "host_s": {"tokenize_cpu": stats.tokenize_cpu_s, "format_cpu": stats.format_cpu_s, "write_cpu": stats.write_cpu_s},
                 "text_bytes": [int(x) for x in stats.text_bytes],
+                "devtok_lines": st.devtok_lines(),
             }
             self.unsupported = st.unsupported()
             if not self.quiet:
