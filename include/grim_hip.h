@@ -695,6 +695,30 @@ int grim_search_run(grim_search *s, grim_batch *donors, const uint32_t *donor_id
 /* the same with donors given as host records, donor_ids[n] */
 int grim_search_run_records(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows,
                             const uint32_t *donor_ids);
+/* The merge door: hit lists that another search produced (a rank's, a saved one, one folded on the host) become inputs of the
+ * same selection.  hits[(l * n_patients + p) * top_n + k], n_hits[l * n_patients + p]: n_lists lists in the layout the results
+ * call below writes, each with this search's own top_n slots per patient (host memory); synchronous.
+ *   Entries: of list l and patient p the first n_hits slots are entries (donor, rec); later slots are not looked at.
+ *   Candidates: an entry is a candidate iff rec.mm[0] >= min_p0, the search's own threshold; a list made under a lower
+ *     threshold is filtered.  The patients' flags are not consulted: a hit is a record some search computed, on the device or on
+ *     allele text.
+ *   Selection: the new running list of patient p is the first top_n, in the strict order above, of (its running list so far)
+ *     united with (the candidates of all lists).  Records and ids are copied bit for bit, reserved = 0; unused slots are
+ *     GRIM_SEARCH_NO_DONOR with a zero record; no floating-point operation is added.  Runs and merges that follow see the merged
+ *     list as the running list.
+ *   Distinct ids over everything a search has seen remain the caller's duty, as for runs.  A repeat across lists is not
+ *     detected: both entries are kept and nothing faults.
+ *   Left alone: the eight summed statistics; the donors and flags calls still speak of the last run and the matcher is not
+ *     touched.  The two device times become the merge's, between the search's own event pair.
+ *   Answers -3 with a text, checked on the host before any upload and after the two times were cleared, the running lists and
+ *     sums exactly as they were: n_patients is not the number of patients set; a null array with something to read; n_lists
+ *     above GRIM_SEARCH_MERGE_MAX_LISTS; some n_hits above top_n; an entry with donor = GRIM_SEARCH_NO_DONOR or reserved != 0;
+ *     an entry whose mm[0] or mm[1] is NaN, infinite or < 0; a list whose entries are not in the strict order for some patient
+ *     (entry k + 1 must come after entry k; this also catches an id repeated within a list).
+ *   Answers 0 and changes nothing when n_lists is 0 or there are no patients; -1 for a null handle, and for a failed device
+ *     call or allocation, which changes nothing: the lists change hands only after everything has worked. */
+#define GRIM_SEARCH_MERGE_MAX_LISTS 4096u
+int grim_search_merge_hits(grim_search *s, const grim_search_hit *hits, const uint32_t *n_hits, uint32_t n_patients, uint32_t n_lists);
 /* hits[patients * top_n], n_hits[patients], over all runs so far; a null pointer skips that part */
 int grim_search_results(grim_search *s, grim_search_hit *hits, uint32_t *n_hits);
 /* patient_flags[patients], donor_flags[donors of the last run]; a null pointer skips that part */

@@ -2848,6 +2848,8 @@ struct grim_search {
   int cur;
   bool have_running;  // [cur] holds lists (false: every list is empty, nothing on the device says so)
   DevBuf<unsigned long long> d_cand;
+  DevBuf<SrHit> d_in;  // the hit lists of a merge and their counts, as uploaded
+  DevBuf<uint32_t> d_in_cnt;
   uint64_t sum[8];  // the matcher's seven counters summed over the runs, [7] candidates
   Events<2> ev;
   double select_ms, kernel_ms;  // of the last run
@@ -2972,7 +2974,7 @@ static int sr_select(grim_search *s, const char *who, const uint32_t *ids, uint3
   }
   for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
     hipLaunchKernelGGL(sr_gather_kernel, dim3(np), dim3(64), 0, st, s->d_keys[side], s->d_cnt[side], lists, m->d_out, n_p, p0, n, hits_were,
-                       top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt]);
+                       top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt], (const SrHit *)nullptr, 0u);
   });
   HIPCHK(hipGetLastError(), c, -1);
   HIPCHK(hipEventRecord(s->ev[1], st), c, -1);
@@ -3013,6 +3015,119 @@ extern "C" int grim_search_run_records(grim_search *s, const grim_subject_result
   const int rc = grim_match_run_records(s->m, res, n, rows, n_rows);
   if (rc != 0) return rc;
   return sr_select(s, "grim_search_run_records", donor_ids, s->m->n_donors);
+}
+
+static_assert(sizeof(SrHit) == sizeof(grim_search_hit) && sizeof(SrHit) == 136 && SR_MERGE_MAX_LISTS == GRIM_SEARCH_MERGE_MAX_LISTS,
+              "hit layout and the bound of a merge");
+static_assert((uint64_t)SR_MERGE_MAX_LISTS * GRIM_SEARCH_MAX_N <= SR_SRC_IN && (SR_SRC_IN & SR_SRC_PREV) == 0,
+              "a slot index l * top_n + k of a merge stays below the SR_SRC_IN tag bit");
+
+// the door of a merge: hit lists as the results are laid out, checked on the host before anything is uploaded; the caller
+// returns -3
+static bool hits_door(grim_ctx *c, const char *who, const grim_search_hit *hits, const uint32_t *n_hits, uint32_t n_p, uint32_t n_lists,
+                      uint32_t top_n) {
+  const uint64_t lists = (uint64_t)n_lists * n_p;
+  if (lists && !n_hits) return refuse(c, who, "n_hits is null with lists to read");
+  for (uint64_t at = 0; at < lists; ++at) {
+    const uint32_t n = n_hits[at];
+    if (n > top_n) return refuse(c, who, "a list with more hits than top_n");
+    if (n && !hits) return refuse(c, who, "hits is null with hits to read");
+    const grim_search_hit *h = hits + at * top_n;
+    for (uint32_t k = 0; k < n; ++k) {
+      if (h[k].donor == GRIM_SEARCH_NO_DONOR || h[k].reserved != 0)
+        return refuse(c, who, "a hit whose donor is GRIM_SEARCH_NO_DONOR or whose reserved word is not 0");
+      for (int q = 0; q < 2; ++q)
+        if (!(h[k].rec.mm[q] >= 0.0 && h[k].rec.mm[q] <= 1.7976931348623157e308))
+          return refuse(c, who, "a hit whose mm[0] or mm[1] is negative, NaN or infinite");
+      if (k && !sr_before(h[k - 1].rec.mm[0], h[k - 1].rec.mm[1], h[k - 1].donor, h[k].rec.mm[0], h[k].rec.mm[1], h[k].donor))
+        return refuse(c, who, "a list whose hits are not in the strict order (mm[0] down, mm[1] down, id up)");
+    }
+  }
+  return true;
+}
+
+extern "C" int grim_search_merge_hits(grim_search *s, const grim_search_hit *hits, const uint32_t *n_hits, uint32_t n_patients,
+                                      uint32_t n_lists) {
+  if (!s) return -1;
+  const char *who = "grim_search_merge_hits";
+  grim_ctx *c = s->ctx;
+  grim_match *m = s->m;
+  s->select_ms = s->kernel_ms = 0.0;
+  const uint32_t n_p = m->P.n, top_n = s->top_n, tile = s->tile, per = tile / top_n;
+  if (n_patients != n_p) {
+    refuse(c, who, "n_patients is not the number of patients set");
+    return -3;
+  }
+  if (n_lists > GRIM_SEARCH_MERGE_MAX_LISTS) {
+    refuse(c, who, "more lists than GRIM_SEARCH_MERGE_MAX_LISTS");
+    return -3;
+  }
+  if (!hits_door(c, who, hits, n_hits, n_p, n_lists, top_n)) return -3;
+  if (n_lists == 0 || n_p == 0) return 0;
+  use_device(c->device);
+  hipStream_t st = c->stream;
+  const uint64_t in_lists = (uint64_t)n_lists * n_p, lists0 = (uint64_t)n_p * (n_lists + 1ull);
+  bool ok = s->d_in.reserve(in_lists * top_n + 1) && s->d_in_cnt.reserve(in_lists + 1) &&  // never an empty allocation
+            reserve_all(lists0, 0, s->d_cnt[0], s->d_cnt[1]) && reserve_all(lists0 * top_n, 0, s->d_keys[0], s->d_keys[1]);
+  if (ok && s->have_running && (uint64_t)n_p > s->d_run_cnt[0].cap) {  // as in sr_select: growing would discard the lists
+    set_err(c, std::string(who) + ": the running lists are smaller than the patients (internal)");
+    return -1;
+  }
+  ok = ok && reserve_all((uint64_t)n_p * top_n, 0, s->d_hits[0], s->d_hits[1], s->d_run_keys[0], s->d_run_keys[1]) &&
+       reserve_all(n_p, 0, s->d_run_cnt[0], s->d_run_cnt[1]);
+  if (!ok) {
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
+  }
+  const int cur = s->cur, nxt = cur ^ 1;
+  // everything that is queued: a failure in it must not return while a staged copy or a kernel is still in flight against
+  // the caller's arrays or the scratch lists, so the stream is drained on that path too
+  auto enqueue = [&]() -> int {
+    // a hits array may be null when every count is 0: the import kernel then reads no hit
+    if (hits) HIPCHK(hipMemcpyAsync(s->d_in, hits, sizeof(grim_search_hit) * in_lists * top_n, hipMemcpyHostToDevice, st), c, -1);
+    HIPCHK(hipMemcpyAsync(s->d_in_cnt, n_hits, 4ull * in_lists, hipMemcpyHostToDevice, st), c, -1);
+    HIPCHK(hipEventRecord(s->ev[0], st), c, -1);
+    const SrKey *extra = s->have_running ? s->d_run_keys[cur].p : nullptr;
+    const uint32_t *extra_cnt = s->have_running ? s->d_run_cnt[cur].p : nullptr;
+    const SrHit *hits_were = s->have_running ? s->d_hits[cur].p : nullptr;
+    const uint32_t in_slots = n_lists * top_n;  // <= 2^20
+    for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
+      hipLaunchKernelGGL(sr_import_kernel, dim3((in_slots + SR_THREADS - 1) / SR_THREADS, np), dim3(SR_THREADS), 0, st, s->d_in, s->d_in_cnt, n_p,
+                         p0, n_lists, top_n, s->min_p0, s->d_keys[0], s->d_cnt[0]);
+    });
+    int side = 0;  // d_keys[side] holds the lists of the level just written
+    uint32_t lists = n_lists;
+    do {  // merging levels, at least one: what the gather reads is one sorted list
+      const uint32_t out_lists = (lists + (extra ? 1u : 0u) + per - 1) / per;
+      for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
+        hipLaunchKernelGGL(sr_tile_kernel, dim3(out_lists, np), dim3(SR_THREADS), 0, st, (const double *)nullptr, (const uint32_t *)nullptr,
+                           (const uint8_t *)nullptr, (const uint8_t *)nullptr, n_p, p0, 0u, s->min_p0, s->d_keys[side], s->d_cnt[side], lists,
+                           extra, extra_cnt, tile, top_n, s->d_keys[side ^ 1], s->d_cnt[side ^ 1], s->d_cand);
+      });
+      side ^= 1;
+      lists = out_lists;
+      extra = nullptr;
+      extra_cnt = nullptr;
+    } while (lists > 1u);
+    for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
+      hipLaunchKernelGGL(sr_gather_kernel, dim3(np), dim3(64), 0, st, s->d_keys[side], s->d_cnt[side], lists, (const double *)nullptr, n_p, p0,
+                         0u, hits_were, top_n, s->d_hits[nxt], s->d_run_keys[nxt], s->d_run_cnt[nxt], s->d_in.p, in_slots);
+    });
+    HIPCHK(hipGetLastError(), c, -1);
+    HIPCHK(hipEventRecord(s->ev[1], st), c, -1);
+    return 0;
+  };
+  if (enqueue() != 0) {
+    (void)hipStreamSynchronize(st);
+    return -1;
+  }
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]), c, -1);
+  s->cur = nxt;
+  s->have_running = true;
+  s->select_ms = s->kernel_ms = ms;
+  return 0;
 }
 
 extern "C" int grim_search_results(grim_search *s, grim_search_hit *hits, uint32_t *n_hits) {

@@ -20,8 +20,30 @@
 //     reset; the other slots are donor = 0xFFFFFFFF with a zero record.  Results are patient-major.
 //   Statistics: grim_match.h's seven counters summed over the runs, and `candidates`, the pairs that passed the threshold,
 //     counted as u64 on the device.
+//   Merge (the merge door of include/grim_hip.h): n_lists hit lists in the layout of the results, in[(l * n_p + p) * top_n + k]
+//     with counts in_cnt[l * n_p + p], each with this search's top_n slots per patient, n_lists <= SR_MERGE_MAX_LISTS.
+//     Entries: the first in_cnt slots of list l and patient p are entries (donor, rec); later slots are not looked at.
+//     Candidates: an entry is a candidate iff rec.mm[0] >= min_p0, the search's own threshold; a list made under a lower one
+//       is filtered.  The patients' flags are not consulted: a hit is a record some search computed.
+//     Selection: the patient's new running list is the first top_n, in the strict order, of (its running list so far) united
+//       with (the candidates of all lists).  Records and ids are copied bit for bit, reserved = 0; unused slots are
+//       donor = 0xFFFFFFFF with a zero record; no floating-point operation is added.  Runs and merges that follow see the
+//       merged list as the running list.
+//     Ids distinct over everything the search has seen stay the caller's duty; a repeat across lists is not detected: both
+//       entries are kept and nothing faults.
+//     Left alone: the eight summed statistics, the matcher and its flags and donors (they speak of the last run).  The two
+//       times become the merge's device time.
+//     The host refuses, before any upload: another number of patients, a null array with something to read, too many lists, a
+//       count above top_n, an entry with donor = 0xFFFFFFFF or reserved != 0, an entry whose mm[0] or mm[1] is NaN, infinite
+//       or < 0, and a list whose entries are not in the strict order (entry k + 1 after entry k under sr_before; this catches
+//       an id repeated within a list).  So the kernels meet only finite values >= 0 here too.
 //
 // Deliberately plain: no floating-point atomics, no inline assembly, one integer atomic per level-0 tile for the statistic.
+//   sr_import_kernel  grid (slots of all lists, patients): one thread per uploaded slot, coalesced over the slot index.  Reads
+//                     mm[0], mm[1] and the id of its hit (stride 136 bytes) and its list's count (clamped to top_n) and writes
+//                     one key entry into the key lists a merging level reads: a candidate with the source index SR_SRC_IN |
+//                     (l * top_n + k), everything else as a sentinel; writes the per-list counts too.  The merging levels of
+//                     a merge are sr_tile_kernel on those lists, with the running list as `extra`; at least one level runs.
 //   sr_tile_kernel    grid (tiles, patients).  A workgroup takes one tile of a patient's candidate stream, builds one key entry
 //                     per candidate in LDS (mm0, mm1, id, and a source index saying where the full record lies: 24 bytes an
 //                     entry, 48 KB at SR_TILE), makes everything else, up to a power of two, a sentinel that sorts last, sorts
@@ -33,7 +55,8 @@
 //                     earlier runs enters the first merging level as one more list (`extra`).  Levels repeat until one list
 //                     per patient is left; 2 top_n <= tile guarantees progress.
 //   sr_gather_kernel  one workgroup per patient: copies the 128-byte records of the kept entries into the new running hit list,
-//                     from this run's result buffer or from the previous running list as the source index says, writes the
+//                     from this run's result buffer, from the previous running list or (SR_SRC_IN, a merge) from the uploaded
+//                     hit lists as the source index says, writes the
 //                     running list's keys for the next run, n_hits and the unused slots.  The running list is double-buffered:
 //                     no kernel reads what it writes.
 //   Every loop bound is a count read once; every index taken from device data (a list's count, a source index) is checked
@@ -45,7 +68,10 @@
 #define SR_THREADS 256u
 #define SR_SENTINEL 0xFFFFFFFFu    // source index of an entry that is no candidate
 #define SR_SRC_PREV 0x80000000u    // source index: slot (low bits) of the patient's previous running list, not a donor of this run
+#define SR_SRC_IN 0x40000000u      // source index: slot l * top_n + k (low bits) of the hit lists a merge uploaded; a run's donor
+                                   // indices stay below 2^24
 #define SR_NO_DONOR 0xFFFFFFFFu    // = GRIM_SEARCH_NO_DONOR
+#define SR_MERGE_MAX_LISTS 4096u   // = GRIM_SEARCH_MERGE_MAX_LISTS: lists x top_n stays below 2^20
 
 struct SrKey {  // 24 bytes
   double mm0, mm1;
@@ -58,7 +84,7 @@ struct SrHit {  // = grim_search_hit
 };
 
 // the strict order; a sentinel (mm0 = mm1 = -1.0, id = 0xFFFFFFFF) comes after every candidate, whose mm0 is >= 0
-__device__ __forceinline__ bool sr_before(double a0, double a1, uint32_t ai, double b0, double b1, uint32_t bi) {
+__host__ __device__ __forceinline__ bool sr_before(double a0, double a1, uint32_t ai, double b0, double b1, uint32_t bi) {
   if (a0 > b0) return true;
   if (a0 == b0) {
     if (a1 > b1) return true;
@@ -183,12 +209,42 @@ __global__ __launch_bounds__(SR_THREADS) void sr_tile_kernel(const double *rec, 
   }
 }
 
+// grid (ceil(n_lists * top_n / SR_THREADS), patients of this launch); block SR_THREADS.  One thread per uploaded slot
+// j = l * top_n + k of patient p: in[(l * n_p + p) * top_n + k], in_cnt[l * n_p + p] -> keys[(p * n_lists + l) * top_n + k],
+// counts[p * n_lists + l] (the count clamped to top_n), the layout a merging level of sr_tile_kernel reads.  An entry (k below
+// the count) with mm[0] >= min_p0 becomes a key with src = SR_SRC_IN | j; every other slot a sentinel.
+__global__ __launch_bounds__(SR_THREADS) void sr_import_kernel(const SrHit *in, const uint32_t *in_cnt, uint32_t n_p, uint32_t p0,
+                                                               uint32_t n_lists, uint32_t top_n, double min_p0, SrKey *keys,
+                                                               uint32_t *counts) {
+  const uint32_t p = p0 + blockIdx.y;
+  const uint64_t j = (uint64_t)blockIdx.x * SR_THREADS + threadIdx.x;
+  if (p >= n_p || top_n == 0u || n_lists > SR_MERGE_MAX_LISTS || j >= (uint64_t)n_lists * top_n) return;
+  const uint32_t l = (uint32_t)(j / top_n), k = (uint32_t)(j % top_n);  // l < n_lists
+  uint32_t cnt = in_cnt[(uint64_t)l * n_p + p];
+  if (cnt > top_n) cnt = top_n;
+  SrKey key = {-1.0, -1.0, 0xFFFFFFFFu, SR_SENTINEL};
+  if (k < cnt) {
+    const SrHit *h = in + ((uint64_t)l * n_p + p) * top_n + k;
+    const double x0 = h->rec[0];
+    if (x0 >= min_p0) {
+      key.mm0 = x0;
+      key.mm1 = h->rec[1];
+      key.id = h->donor;
+      key.src = SR_SRC_IN | (uint32_t)j;  // j < 2^20
+    }
+  }
+  keys[((uint64_t)p * n_lists + l) * top_n + k] = key;
+  if (k == 0u) counts[(uint64_t)p * n_lists + l] = cnt;
+}
+
 // grid (patients of this launch); block 64.  keys[p * stride * top_n + k], counts[p * stride]: the patient's one list left.
 // rec = this run's records [n_p][n_d]; prev = the previous running list [n_p][top_n] (read only when a source index says so);
-// out = the new one, okeys / ocnt its keys and count for the next run.
+// in = the hit lists of a merge, in[(l * n_p + p) * top_n + k] for the source index SR_SRC_IN | (l * top_n + k), which must be
+// below in_slots = n_lists * top_n (a run passes null / 0); out = the new one, okeys / ocnt its keys and count for the next run.
 __global__ __launch_bounds__(64) void sr_gather_kernel(const SrKey *keys, const uint32_t *counts, uint32_t stride, const double *rec,
                                                        uint32_t n_p, uint32_t p0, uint32_t n_d, const SrHit *prev, uint32_t top_n,
-                                                       SrHit *out, SrKey *okeys, uint32_t *ocnt) {
+                                                       SrHit *out, SrKey *okeys, uint32_t *ocnt, const SrHit *in,
+                                                       uint32_t in_slots) {
   const uint32_t p = p0 + blockIdx.x, lane = threadIdx.x;
   if (p >= n_p) return;
   uint32_t cnt = counts[(uint64_t)p * stride];  // read once
@@ -205,6 +261,9 @@ __global__ __launch_bounds__(64) void sr_gather_kernel(const SrKey *keys, const 
         if (key.src & SR_SRC_PREV) {
           const uint32_t slot = key.src & ~SR_SRC_PREV;
           if (prev != nullptr && slot < top_n) from = prev[(uint64_t)p * top_n + slot].rec;
+        } else if (in != nullptr && (key.src & SR_SRC_IN)) {
+          const uint32_t j = key.src & ~SR_SRC_IN;
+          if (j < in_slots) from = in[((uint64_t)(j / top_n) * n_p + p) * top_n + j % top_n].rec;
         } else if (key.src < n_d) {
           from = rec + ((uint64_t)p * n_d + key.src) * MT_REC;
         }

@@ -682,7 +682,7 @@ class Matcher(_Handle):
 EXPORTS += [
     "grim_search_create", "grim_search_set_patients", "grim_search_reset", "grim_search_run", "grim_search_run_records",
     "grim_search_results", "grim_search_flags", "grim_search_patients", "grim_search_donors", "grim_search_top_n",
-    "grim_search_stats", "grim_search_kernel_ms", "grim_search_select_ms", "grim_search_free",
+    "grim_search_stats", "grim_search_kernel_ms", "grim_search_select_ms", "grim_search_free", "grim_search_merge_hits",
 ]
 
 SEARCH_DT = np.dtype([("donor", "<u4"), ("reserved", "<u4"), ("rec", MATCH_DT)])
@@ -690,6 +690,7 @@ assert SEARCH_DT.itemsize == 136
 SEARCH_MAX_N = 256
 SEARCH_TILE = 2048  # entries a workgroup sorts at a time (GRIM_SEARCH_TILE lowers it, for tests)
 SEARCH_NO_DONOR = 0xFFFFFFFF
+SEARCH_MERGE_MAX_LISTS = 4096
 SEARCH_STATS = MATCH_STATS + ("candidates",)
 
 _search_ready = False
@@ -722,6 +723,8 @@ def _search_lib():
             getattr(L, name).restype = C.c_double
             getattr(L, name).argtypes = [C.c_void_p]
         L.grim_search_free.argtypes = [C.c_void_p]
+        L.grim_search_merge_hits.restype = C.c_int
+        L.grim_search_merge_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         _search_ready = True
     return L
 
@@ -772,6 +775,20 @@ class Searcher(_Handle):
         res, rows, args = _records(res, rows)
         ids = self._ids(ids, res.shape[0])
         self._check(_search_lib().grim_search_run_records(self.h, *args, _ptr(ids) if ids.size else None), "grim_search_run_records")
+
+    def merge(self, hits, n_hits):
+        """hit lists that another search produced into the running lists (grim_search_merge_hits): hits SEARCH_DT[L][P][top_n]
+        or [P][top_n], n_hits u32[L][P] or [P], P and top_n this search's; results() speaks of them from now on, stats(),
+        flags() and donors() do not; kernel_ms() and select_ms() become the merge's device time"""
+        hits = np.ascontiguousarray(hits, dtype=SEARCH_DT)
+        n_hits = np.ascontiguousarray(n_hits, dtype=np.uint32)
+        if hits.ndim == 2:
+            hits, n_hits = hits[None], n_hits[None]
+        if hits.ndim != 3 or hits.shape[2] != self.top_n() or n_hits.shape != hits.shape[:2]:
+            raise ValueError("hits of shape %r with n_hits of shape %r: not [lists][patients][top_n = %d] with one count a list"
+                             % (hits.shape, n_hits.shape, self.top_n()))
+        self._check(_search_lib().grim_search_merge_hits(self.h, _ptr(hits) if hits.size else None, _ptr(n_hits) if n_hits.size else None,
+                                                         hits.shape[1], hits.shape[0]), "grim_search_merge_hits")
 
     def patients(self):
         return int(_search_lib().grim_search_patients(self.h))

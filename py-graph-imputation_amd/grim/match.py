@@ -252,7 +252,7 @@ class _Pairing:
         self.g = g = imputation.netGraph
         self.mask = _keep_mask(g.locus_slot, keep_loci)
         self.slots = _slots_of(self.mask)
-        self.dlines = read_lines(donor_lines_or_path)
+        self.dlines = [] if donor_lines_or_path is None else read_lines(donor_lines_or_path)  # None: given per donor_blocks call
         self.plines = [l.rstrip("\n") for l in patient_lines]
         if len(self.plines) > nat.MATCH_MAX_PAIRS:
             raise ValueError("%d patients: more than %d pairs with a single donor" % (len(self.plines), nat.MATCH_MAX_PAIRS))
@@ -281,8 +281,12 @@ class _Pairing:
         stats["patients_valid"] = int(np.count_nonzero(self.pf & nat.MATCH_VALID))
         stats["patients_private"] = int(np.count_nonzero(self.pf & nat.MATCH_PRIVATE))
 
-    def donor_blocks(self):
-        self._cut = self.blocks.cut(self.dlines, self.block_lines)
+    def donor_blocks(self, lines=None, first=0):
+        """the blocks of the donor lines given at construction, or of `lines`, which begin at line `first` of the donor input
+        (a consumer that is fed its donors piece by piece); the cut before it is closed"""
+        if self._cut is not None:
+            self._cut.close()
+        self._cut = self.blocks.cut(self.dlines if lines is None else lines, self.block_lines, first)
         return self._cut
 
     def check(self, block, flags):

@@ -17,6 +17,10 @@ not depend on how the donors are cut into runs or in which order the runs come.
 HBM, and patients x top_n hits come down once, after the last block.  `search_records` is the same selection over record
 arrays in plain Python, laid out as the device lays it out; `search_umug_text` the same over `.umug` text.  The three agree
 bit for bit.  There is no CPU fallback of the device functions.
+
+The first N of a union are among the first N of each part, so hit lists that other searches produced are inputs of the same
+selection: `DonorSearch` is `search_donors` opened once, fed its donors piece by piece and given such lists through the
+device's merge door (`nat.Searcher.merge`); `merge_hit_lists` is that door's twin in plain Python.
 """
 
 import math
@@ -75,6 +79,72 @@ def search_records(pres, prows, donor_runs, keep_mask, n_alleles, top_n, min_p0)
     return hits, n_hits, stats
 
 
+def _as_lists(lists, top_n):
+    """`lists` of merge_hit_lists -> [(hits SEARCH_DT[P][top_n], n_hits u32[P])]"""
+    if isinstance(lists, tuple) and len(lists) == 2 and isinstance(lists[0], np.ndarray) and lists[0].ndim == 3:
+        lists = list(zip(lists[0], lists[1]))  # (hits[L][P][top_n], n_hits[L][P])
+    out = []
+    for hits, n_hits in lists:
+        hits, n_hits = np.asarray(hits), np.asarray(n_hits)
+        if hits.dtype != nat.SEARCH_DT or hits.ndim != 2 or hits.shape[1] != top_n or n_hits.shape != hits.shape[:1]:
+            raise ValueError("a list is not (nat.SEARCH_DT[patients][top_n = %d], one count a patient)" % top_n)
+        out.append((hits, n_hits))
+    return out
+
+
+def merge_hit_lists(lists, top_n, min_p0, running=None):
+    """The merge door of the device search (grim_search_merge_hits, include/grim_hip.h) in plain Python.  `lists`: a sequence
+    of (hits nat.SEARCH_DT[P][top_n], n_hits[P]) as `search_records`, `Searcher.results` or `DonorSearch.hits` give them, or
+    one pair of arrays (hits[L][P][top_n], n_hits[L][P]); `running`: the (hits, n_hits) the search holds so far, taken as it
+    is (None: empty lists).  Of every list and patient the first n_hits slots are entries; an entry is a candidate iff its
+    mm[0] >= min_p0; the answer per patient is the first top_n of running + candidates in the search's order ->
+    (hits nat.SEARCH_DT[P][top_n], n_hits u32[P]), laid out as the device lays them out.  The refusals of the door are
+    ValueErrors here: lists for another number of patients, more than nat.SEARCH_MERGE_MAX_LISTS lists, a count above top_n,
+    an entry with donor = nat.SEARCH_NO_DONOR or reserved != 0, an entry whose mm[0] or mm[1] is NaN, infinite or < 0, a list
+    whose entries are not in the strict order."""
+    top_n, min_p0 = _check(top_n, min_p0)
+    lists = _as_lists(lists, top_n)
+    if running is not None:
+        running = _as_lists([running], top_n)[0]
+    if not lists and running is None:
+        raise ValueError("neither lists nor a running list: the number of patients is not known")
+    n_p = len(running[1]) if running is not None else len(lists[0][1])
+    if len(lists) > nat.SEARCH_MERGE_MAX_LISTS:
+        raise ValueError("%d lists: more than %d" % (len(lists), nat.SEARCH_MERGE_MAX_LISTS))
+    found = [[] for _ in range(n_p)]  # per patient: ((-mm0, -mm1, id), hit)
+    for l, (hits, n_hits) in enumerate(lists):
+        if len(n_hits) != n_p:
+            raise ValueError("list %d is of %d patients, not %d" % (l, len(n_hits), n_p))
+        if len(n_hits) and int(n_hits.max()) > top_n:
+            raise ValueError("list %d holds a count above top_n" % l)
+        for p in np.flatnonzero(n_hits):
+            before = None
+            for h in hits[p, :int(n_hits[p])]:
+                mm0, mm1, donor = float(h["rec"]["mm"][0]), float(h["rec"]["mm"][1]), int(h["donor"])
+                if donor == nat.SEARCH_NO_DONOR or int(h["reserved"]) != 0:
+                    raise ValueError("list %d, patient %d: a hit whose donor is SEARCH_NO_DONOR or whose reserved word is not 0" % (l, p))
+                if not (0.0 <= mm0 < math.inf and 0.0 <= mm1 < math.inf):
+                    raise ValueError("list %d, patient %d: a hit whose mm[0] or mm[1] is negative, NaN or infinite" % (l, p))
+                key = (-mm0, -mm1, donor)
+                if before is not None and not before < key:
+                    raise ValueError("list %d, patient %d: the hits are not in the strict order (mm[0] down, mm[1] down, id up)" % (l, p))
+                before = key
+                if mm0 >= min_p0:
+                    found[p].append((key, h))
+    out = _empty_hits(n_p, top_n)
+    n_out = np.zeros(n_p, dtype=np.uint32)
+    for p, cands in enumerate(found):
+        if running is not None:
+            cands += [((-float(h["rec"]["mm"][0]), -float(h["rec"]["mm"][1]), int(h["donor"])), h)
+                      for h in running[0][p, :min(top_n, int(running[1][p]))]]
+        cands.sort(key=lambda c: c[0])
+        n_out[p] = min(top_n, len(cands))
+        for k, (key, h) in enumerate(cands[:top_n]):
+            out[p, k]["donor"] = key[2]
+            out[p, k]["rec"] = h["rec"]
+    return out, n_out
+
+
 def search_umug_text(patient_text, donor_text, keep_loci, top_n, min_p0=0.0):
     """The selection on `.umug` text through `match_umug_text`; a donor's id is its position in the donor text -> (patient ids,
     donor ids, hits): hits[p] is the list of (donor position, mm[0..2|K|], {locus name: probability of no mismatch}) of the
@@ -87,6 +157,118 @@ def search_umug_text(patient_text, donor_text, keep_loci, top_n, min_p0=0.0):
         cands.sort()
         hits.append([(d,) + line[d] for _, _, d in cands[:top_n]])
     return pid, did, hits
+
+
+class DonorSearch:
+    """`search_donors` opened once: the patients are imputed as one device batch and set at construction; `feed` streams donor
+    lines through the device, any number of times; `merge` takes hit lists that another search of the same patients produced;
+    `hits` is the answer over everything fed and merged so far; `close` releases the device objects.  Arguments as
+    `search_donors`, without the donors."""
+
+    def __init__(self, imputation, patient_lines, config, keep_loci, top_n, min_p0=0.0, block_lines=65536, planb=None, em=False):
+        self.top_n, self.min_p0 = _check(top_n, min_p0)
+        self.pairing = pairing = _Pairing(imputation, patient_lines, None, config, keep_loci, block_lines, planb, em)
+        self.searcher = None
+        self.stats = dict.fromkeys(nat.SEARCH_STATS, 0)
+        self.stats.update(blocks=0, kernel_ms=0.0, select_ms=0.0, host_pairs=0, download_bytes=0)
+        self.merge_ms = 0.0  # device time of the merges
+        self.host = {}   # patient -> [((-mm0, -mm1, id), H, L)] of the pairs folded here, at most top_n after a block
+        try:
+            self.searcher = nat.Searcher(pairing.ctx, pairing.mask, pairing.n_alleles, self.top_n, self.min_p0)
+            pairing.set_patients(self.searcher, lambda: self.searcher.flags()[0], self.stats)
+        except BaseException:
+            self.close()
+            raise
+
+    def feed(self, donor_lines, first=0):
+        """donor lines (a list, or the path of an input file) that begin at line `first` of the donor input: cut into blocks,
+        each imputed as one device batch and selected on the device into the running lists; a donor's id is `first` + its
+        position in `donor_lines`"""
+        pairing, searcher, stats, top_n = self.pairing, self.searcher, self.stats, self.top_n
+        dlines = read_lines(donor_lines)
+        first = int(first)
+        if first < 0 or first + len(dlines) >= nat.SEARCH_NO_DONOR:
+            raise ValueError("donor lines %d..%d: a line number must fit a hit's donor field" % (first, first + len(dlines)))
+        pf, host = pairing.pf, self.host
+        for block in pairing.donor_blocks(dlines, first):
+            if block.batch is None or not len(pf):
+                pairing.check(block, np.zeros(0, dtype=np.uint8))
+                continue
+            ids = block.lo + block.line_of
+            searcher.run(block.batch, ids.astype(np.uint32))
+            df = searcher.flags()[1]
+            for p, d, H, L in pairing.host_pairs(block, df):
+                stats["host_pairs"] += 1
+                if H[0] >= self.min_p0:
+                    host.setdefault(int(p), []).append(((-H[0], -H[1], int(ids[d])), H, L))
+                    stats["candidates"] += 1
+            for p in host:
+                host[p].sort(key=lambda c: c[0])
+                del host[p][top_n:]
+            stats["donors_valid"] += int(np.count_nonzero(df & nat.MATCH_VALID))
+            stats["donors_private"] += int(np.count_nonzero(df & nat.MATCH_PRIVATE))
+            stats["kernel_ms"] += searcher.kernel_ms()
+            stats["select_ms"] += searcher.select_ms()
+            stats["blocks"] += 1
+
+    def merge(self, hits, n_hits):
+        """hit lists by patient *line*, as `hits` returns them: nat.SEARCH_DT[L][lines][top_n] or [lines][top_n] with matching
+        n_hits, of searches of the same patients over other donors (ids distinct from everything seen here).  The lines that
+        are patients on the device go through the device's merge door; the other lines have no hits."""
+        hits = np.asarray(hits)
+        n_hits = np.asarray(n_hits, dtype=np.uint32)
+        if hits.ndim == 2:
+            hits, n_hits = hits[None], n_hits[None]
+        lines = len(self.pairing.plines)
+        if hits.dtype != nat.SEARCH_DT or hits.shape[1:] != (lines, self.top_n) or n_hits.shape != hits.shape[:2]:
+            raise ValueError("not nat.SEARCH_DT[lists][%d patient lines][top_n = %d] with one count a list and line" % (lines, self.top_n))
+        if not len(self.pairing.pf):
+            if n_hits.any():
+                raise ValueError("hits of patient lines that are no patients on the device")
+            return
+        line_of = self.pairing.pblock.line_of
+        off = np.ones(lines, dtype=bool)
+        off[line_of] = False
+        if n_hits[:, off].any():
+            raise ValueError("hits of patient lines that are no patients on the device")
+        self.searcher.merge(hits[:, line_of], n_hits[:, line_of])
+        self.merge_ms += self.searcher.select_ms()
+
+    def hits(self):
+        """-> (patient_ok, hits, n_hits, stats) as `search_donors` returns them, over everything fed and merged so far: the
+        device's lists fetched and merged with the pairs folded on the host under the same order"""
+        pairing, top_n = self.pairing, self.top_n
+        plines, slots, pf, pblock, host = pairing.plines, pairing.slots, pairing.pf, pairing.pblock, self.host
+        stats = dict(self.stats)
+        hits = _empty_hits(len(plines), top_n)
+        n_hits = np.zeros(len(plines), dtype=np.uint32)
+        if len(pf):
+            dev_hits, dev_n = self.searcher.results()
+            stats["download_bytes"] = dev_hits.nbytes + dev_n.nbytes
+            total = self.searcher.stats()
+            stats["pairs"], stats["row_pairs"] = total["pairs"], total["row_pairs"]
+            stats["candidates"] += total["candidates"]
+            for p in range(len(pf)):
+                line = int(pblock.line_of[p])
+                if p not in host:
+                    hits[line], n_hits[line] = dev_hits[p], dev_n[p]
+                    continue
+                merged = [((-float(h["rec"]["mm"][0]), -float(h["rec"]["mm"][1]), int(h["donor"])), h) for h in dev_hits[p, :int(dev_n[p])]]
+                merged += [(key, (H, L)) for key, H, L in host[p]]
+                merged.sort(key=lambda c: c[0])
+                n_hits[line] = min(top_n, len(merged))
+                for k, (key, what) in enumerate(merged[:top_n]):
+                    hits[line, k]["donor"] = key[2]
+                    if isinstance(what, tuple):
+                        _store(hits[line, k]["rec"], slots, *what)
+                    else:
+                        hits[line, k]["rec"] = what["rec"]
+        return pairing.patient_ok, hits, n_hits, stats
+
+    def close(self):
+        self.pairing.close()
+        if self.searcher is not None:
+            self.searcher.close()
 
 
 def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_loci, top_n, min_p0=0.0, block_lines=65536, planb=None,
@@ -108,64 +290,25 @@ def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_l
     do not show in any byte.  Subjects the device cannot answer follow `imputation.on_unsupported` as in
     `impute_lines_block`."""
     top_n, min_p0 = _check(top_n, min_p0)
-    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em)
-    plines, slots = pairing.plines, pairing.slots
-    if len(pairing.dlines) >= nat.SEARCH_NO_DONOR:
-        raise ValueError("%d donor lines: a line number must fit a hit's donor field" % len(pairing.dlines))
-    searcher = nat.Searcher(pairing.ctx, pairing.mask, pairing.n_alleles, top_n, min_p0)
-    stats = dict.fromkeys(nat.SEARCH_STATS, 0)
-    stats.update(blocks=0, kernel_ms=0.0, select_ms=0.0, host_pairs=0, download_bytes=0)
-    hits = _empty_hits(len(plines), top_n)
-    n_hits = np.zeros(len(plines), dtype=np.uint32)
+    search = DonorSearch(imputation, patient_lines, config, keep_loci, top_n, min_p0, block_lines, planb, em)
     try:
-        pairing.set_patients(searcher, lambda: searcher.flags()[0], stats)
-        pf, pblock = pairing.pf, pairing.pblock
-        host = {}   # patient -> [((-mm0, -mm1, id), H, L)] of the pairs folded here, at most top_n after a block
-        for block in pairing.donor_blocks():
-            if block.batch is None or not len(pf):
-                pairing.check(block, np.zeros(0, dtype=np.uint8))
-                continue
-            ids = block.lo + block.line_of
-            searcher.run(block.batch, ids.astype(np.uint32))
-            df = searcher.flags()[1]
-            for p, d, H, L in pairing.host_pairs(block, df):
-                stats["host_pairs"] += 1
-                if H[0] >= min_p0:
-                    host.setdefault(int(p), []).append(((-H[0], -H[1], int(ids[d])), H, L))
-                    stats["candidates"] += 1
-            for p in host:
-                host[p].sort(key=lambda c: c[0])
-                del host[p][top_n:]
-            stats["donors_valid"] += int(np.count_nonzero(df & nat.MATCH_VALID))
-            stats["donors_private"] += int(np.count_nonzero(df & nat.MATCH_PRIVATE))
-            stats["kernel_ms"] += searcher.kernel_ms()
-            stats["select_ms"] += searcher.select_ms()
-            stats["blocks"] += 1
-        if len(pf):
-            dev_hits, dev_n = searcher.results()  # once, after the last block
-            stats["download_bytes"] = dev_hits.nbytes + dev_n.nbytes
-            total = searcher.stats()
-            stats["pairs"], stats["row_pairs"] = total["pairs"], total["row_pairs"]
-            stats["candidates"] += total["candidates"]
-            for p in range(len(pf)):
-                line = int(pblock.line_of[p])
-                if p not in host:
-                    hits[line], n_hits[line] = dev_hits[p], dev_n[p]
-                    continue
-                merged = [((-float(h["rec"]["mm"][0]), -float(h["rec"]["mm"][1]), int(h["donor"])), h) for h in dev_hits[p, :int(dev_n[p])]]
-                merged += [(key, (H, L)) for key, H, L in host[p]]
-                merged.sort(key=lambda c: c[0])
-                n_hits[line] = min(top_n, len(merged))
-                for k, (key, what) in enumerate(merged[:top_n]):
-                    hits[line, k]["donor"] = key[2]
-                    if isinstance(what, tuple):
-                        _store(hits[line, k]["rec"], slots, *what)
-                    else:
-                        hits[line, k]["rec"] = what["rec"]
+        search.feed(donor_lines_or_path)
+        return search.hits()
     finally:
-        pairing.close()
-        searcher.close()
-    return pairing.patient_ok, hits, n_hits, stats
+        search.close()
+
+
+def write_hits_csv(out_path, graph, keep_loci, plines, dlines, pok, hits, n_hits):
+    """the CSV of `search_file`: the header, then per patient line with genotype rows its hits in order"""
+    slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
+    nb = 2 * len(slots) + 1
+    with open(out_path, "w") as fh:
+        fh.write(",".join(["patient_id", "rank", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots]) + "\n")
+        for p in np.flatnonzero(pok):
+            for k in range(int(n_hits[p])):
+                r = hits[p, k]["rec"]
+                vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
+                fh.write("%s,%d,%s,%s\n" % (line_id(plines[p]), k, line_id(dlines[int(hits[p, k]["donor"])]), ",".join(repr(v) for v in vals)))
 
 
 def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, graph=None, block_lines=65536):
@@ -183,13 +326,5 @@ def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0
     imp = Imputation(graph, config)
     plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
     pok, hits, n_hits, stats = search_donors(imp, plines, dlines, config, keep_loci, top_n, min_p0=min_p0, block_lines=block_lines)
-    slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
-    nb = 2 * len(slots) + 1
-    with open(out_path, "w") as fh:
-        fh.write(",".join(["patient_id", "rank", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots]) + "\n")
-        for p in np.flatnonzero(pok):
-            for k in range(int(n_hits[p])):
-                r = hits[p, k]["rec"]
-                vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
-                fh.write("%s,%d,%s,%s\n" % (line_id(plines[p]), k, line_id(dlines[int(hits[p, k]["donor"])]), ",".join(repr(v) for v in vals)))
+    write_hits_csv(out_path, graph, keep_loci, plines, dlines, pok, hits, n_hits)
     return stats

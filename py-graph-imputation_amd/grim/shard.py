@@ -714,6 +714,231 @@ def em_fixed_support_sharded(conf_file, iterations, chunk_lines=None, tol=None, 
     return out
 
 
+# ---- the sharded donor search: every rank's hit lists onto the store, merged by rank 0 on the device ----------------
+SEARCH_SUMS = ("donors_valid", "donors_private", "pairs", "row_pairs", "candidates", "host_pairs", "kernel_ms", "select_ms", "blocks",
+               "download_bytes")
+
+
+def _pack_hits(patient_ok, hits, n_hits, stats, unsupported):
+    """a rank's (or the job's) hit lists as bytes: a JSON head (Python writes a float so that it reads back the same) and the
+    raw hits / n_hits bytes"""
+    import struct
+
+    import numpy as np
+
+    from . import _native as nat
+
+    hits = np.ascontiguousarray(hits, dtype=nat.SEARCH_DT)
+    n_hits = np.ascontiguousarray(n_hits, dtype="<u4")
+    head = json.dumps({"patients": int(hits.shape[0]), "top_n": int(hits.shape[1]), "ok": [int(x) for x in patient_ok], "stats": stats,
+                       "unsupported": [list(u) for u in unsupported]}).encode()
+    return struct.pack("<Q", len(head)) + head + hits.tobytes() + n_hits.tobytes()
+
+
+def _unpack_hits(blob):
+    import struct
+
+    import numpy as np
+
+    from . import _native as nat
+
+    (n_head,) = struct.unpack_from("<Q", blob, 0)
+    head = json.loads(blob[8:8 + n_head].decode())
+    n_p, top_n, at = head["patients"], head["top_n"], 8 + n_head
+    size = nat.SEARCH_DT.itemsize * n_p * top_n
+    if len(blob) != at + size + 4 * n_p:
+        raise RuntimeError("search_sharded: hit lists of %d patients x %d in %d bytes" % (n_p, top_n, len(blob) - at))
+    hits = np.frombuffer(blob, dtype=nat.SEARCH_DT, count=n_p * top_n, offset=at).reshape(n_p, top_n).copy()
+    n_hits = np.frombuffer(blob, dtype="<u4", count=n_p, offset=at + size).copy()
+    return np.array(head["ok"], dtype=bool), hits, n_hits, head["stats"], [tuple(u) for u in head["unsupported"]]
+
+
+def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk_lines=None, graph=None, compute=None, timeout_s=1800,
+                   block_lines=65536):
+    """The donor search (grim.search.search_donors) across the ranks of the torch.distributed job, or alone if there is none:
+    the configuration's input file as donors against the input file `patients_path`.  Every rank builds its graph and opens
+    one grim.search.DonorSearch over all patients; the ranks pull donor chunks of `chunk_lines` lines from the job's counter
+    as `impute_sharded` cuts them and feed each with its first line's number, so a donor's id is its line in the input file
+    and the device accumulates across a rank's chunks.  Ranks other than 0 publish their hit lists on the job's store; rank 0
+    merges them into its own through the device's merge door (DonorSearch.merge, one call), takes the answer and publishes it.
+    -> (patient_ok, hits, n_hits, stats) on EVERY rank, decoded from the same bytes, as `search_donors` returns them: hits
+    and n_hits do not depend on chunk_lines, on the world size, on which rank ran which chunk, or on block_lines; alone it
+    equals `search_donors`.  In stats the pair counters (donors_valid, donors_private, pairs, row_pairs, candidates,
+    host_pairs) are sums over the ranks and equal `search_donors`'; patients_* and undefined are rank 0's; kernel_ms,
+    select_ms, blocks and download_bytes are summed; `chunks`, `merge_ms` (device time of rank 0's merge) and `unsupported`
+    (the donor subjects of all ranks, by input line, that GRIM_ON_UNSUPPORTED=skip let the job go on without) are added, and
+    `patients_unsupported`, the same of the patients' file.
+
+    `compute(config, patient_lines, donor_lines, first) -> (hits, n_hits, stats)` can be injected (tests): a rank then folds
+    its chunks' lists, and rank 0 the ranks' lists, with grim.search.merge_hit_lists.  Every wait ends `timeout_s` seconds
+    after the call began at the latest, or when a peer reports an error; every rank raises when any rank failed."""
+    import numpy as np
+
+    from .blocks import read_lines
+    from .em import chunk_text_lines
+    from .run_impute_def import load_config
+    from .search import _check, _empty_hits, merge_hit_lists
+
+    top_n, min_p0 = _check(top_n, min_p0)
+    ctl = _Control(timeout_s)
+    chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
+    error = peer_failed = None
+    result = blob = None
+    tag = ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
+    search = None
+    try:
+        config, _ = load_config(conf_file)
+        in_path = config["imputation_input_file"]
+        offs = chunk_offsets(in_path, chunk_lines)
+        n_chunks = len(offs) - 1
+        plines = read_lines(patients_path)
+        imp = None
+        patients_bad = []
+        if compute is None:
+            from . import _native as nat
+            from .imputation.impute import Imputation as _I
+            from .imputation.networkx_graph import Graph
+            from .search import DonorSearch
+
+            if graph is None:
+                graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
+            n_dev = max(1, nat.lib().grim_device_count())
+            imp = _I(graph, config, device=ctl.local % n_dev)
+            search = DonorSearch(imp, plines, config, keep_loci, top_n, min_p0, block_lines)
+            patients_bad = list(imp.unsupported)
+        else:
+            running = (_empty_hits(len(plines), top_n), np.zeros(len(plines), dtype=np.uint32))
+            sums = dict.fromkeys(SEARCH_SUMS, 0)
+        # ---- this rank's chunks ----------------------------------------------------------------------------------------
+        with open(in_path, "rb") as fh:
+            while True:
+                c = ctl.next_chunk(tag)
+                if c >= n_chunks:
+                    break
+                fh.seek(offs[c])
+                lines = chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
+                if compute is None:
+                    search.feed(lines, first=c * chunk_lines)
+                else:
+                    hits, n_hits, chunk_stats = compute(config, plines, lines, c * chunk_lines)
+                    running = merge_hit_lists([(hits, n_hits)], top_n, min_p0, running=running)
+                    for k in SEARCH_SUMS:
+                        sums[k] += chunk_stats.get(k, 0)
+
+        def mine():
+            if compute is None:
+                ok, hits, n_hits, stats = search.hits()
+                return ok, hits, n_hits, stats, imp.unsupported[len(patients_bad):]
+            return np.ones(len(plines), dtype=bool), running[0], running[1], dict(sums), []
+
+        # ---- ranks other than 0 publish their lists; rank 0 merges them into its own -----------------------------------
+        final = "grim_srf_" + tag
+        if ctl.rank != 0:
+            _publish(ctl, "grim_srl_%s_%d" % (tag, ctl.rank), _pack_hits(*mine()))
+            blob = _collect(ctl, final, tag, False)
+        else:
+            others = [_unpack_hits(_collect(ctl, "grim_srl_%s_%d" % (tag, r), tag, True)) for r in range(1, ctl.world)]
+            for r, part in enumerate(others):
+                if part[1].shape != (len(plines), top_n):
+                    raise RuntimeError("search_sharded: rank %d sent lists of shape %r" % (r + 1, part[1].shape))
+            merge_ms = 0.0
+            if compute is None:
+                if others:
+                    search.merge(np.stack([part[1] for part in others]), np.stack([part[2] for part in others]))
+                    merge_ms = search.merge_ms
+                ok, hits, n_hits, stats, unsupported = mine()
+            else:
+                ok, hits, n_hits, stats, unsupported = mine()
+                hits, n_hits = merge_hit_lists([part[1:3] for part in others], top_n, min_p0, running=(hits, n_hits))
+            unsupported = list(unsupported)
+            for part in others:
+                for k in SEARCH_SUMS:
+                    stats[k] = stats.get(k, 0) + part[3].get(k, 0)
+                unsupported += part[4]
+            stats.update(chunks=n_chunks, merge_ms=merge_ms, patients_unsupported=[list(u) for u in patients_bad])
+            blob = _pack_hits(ok, hits, n_hits, stats, sorted(unsupported))
+            if ctl.world > 1:
+                _publish(ctl, final, blob)
+        ok, hits, n_hits, stats, unsupported = _unpack_hits(blob)  # every rank reads the same bytes
+        stats["unsupported"] = unsupported
+        stats["patients_unsupported"] = [tuple(u) for u in stats["patients_unsupported"]]
+        result = (ok, hits, n_hits, stats)
+    except BaseException as e:  # the other ranks must not wait for this one: report, reach the barrier, raise
+        if isinstance(e, _PeerFailed):
+            peer_failed = e
+        else:
+            error = e
+            ctl.report_error(tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
+    finally:
+        if search is not None:
+            search.close()
+    failed = ctl.barrier_and_errors(tag)
+    try:
+        if error is not None:
+            raise error
+        if failed:
+            raise RuntimeError("search_sharded: rank(s) %s failed:\n%s" % ([r for r, _ in failed], failed[0][1]))
+        if peer_failed is not None:
+            raise peer_failed
+    finally:
+        ctl.barrier()  # nobody leaves while another rank still reads the store
+        if ctl.rank == 0 and ctl.world > 1:
+            _discard(ctl, "grim_srf_" + tag)
+            for r in range(1, ctl.world):  # lists a rank published before the job failed: nobody will collect them
+                _discard(ctl, "grim_srl_%s_%d" % (tag, r))
+    return result
+
+
+def _discard(ctl, name):
+    """best effort: the pieces and the head key of a blob published under `name`, if its head key is there"""
+    try:
+        if ctl._has(name):
+            for i in range(int(ctl.store.get(name))):
+                ctl.delete("%s_%d" % (name, i))
+            ctl.delete(name)
+    except Exception:
+        pass
+
+
+def search_file_sharded(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, chunk_lines=None, graph=None, timeout_s=1800,
+                        block_lines=65536):
+    """grim.search.search_file across the ranks of the job through `search_sharded`: rank 0 writes the CSV at `out_path`, byte
+    for byte the file `search_file` writes; every rank returns when it is written, and every rank raises when rank 0 could
+    not write it.  -> stats, the same on every rank"""
+    from .blocks import read_lines
+    from .imputation.networkx_graph import Graph
+    from .run_impute_def import load_config
+    from .search import write_hits_csv
+
+    config, _ = load_config(conf_file)
+    if graph is None:
+        graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
+    ok, hits, n_hits, stats = search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=min_p0, chunk_lines=chunk_lines, graph=graph,
+                                             timeout_s=timeout_s, block_lines=block_lines)
+    ctl = _Control(timeout_s)
+    failure = []
+
+    def write():  # on rank 0 (or alone) -> what the other ranks learn: "ok" or the error's text
+        try:
+            write_hits_csv(out_path, graph, keep_loci, read_lines(patients_path), read_lines(config["imputation_input_file"]), ok, hits,
+                           n_hits)
+            return "ok"
+        except Exception as e:
+            failure.append(e)
+            return "%s: %s" % (type(e).__name__, e)
+
+    key = "grim_srcsv_%d" % _next_call()
+    text = ctl.share(key, write)
+    ctl.barrier()  # every rank has read the key
+    if ctl.rank == 0:
+        ctl.delete(key)
+    if failure:
+        raise failure[0]
+    if text != "ok":
+        raise RuntimeError("search_file_sharded: rank 0 could not write %s: %s" % (out_path, text))
+    return stats
+
+
 _call_counter = [0]
 
 

@@ -9,8 +9,13 @@ kept; top_n 10 and 256.  One JSON line with medians over --steps steps after --w
   (c) search_bytes        what comes down: patients x top_n x 136, against match_bytes = patients x donors x 128 before
   (d) search_wall_s       wall time of one Searcher run plus results(), against match_wall_s: one Matcher run plus
                           results() on the same batch
+  (e) merge               the merge door at the last patient count and the largest top_n: the donors dealt into --merge-lists
+                          parts, each part's hit list made by a run, then merge_select_ms (grim_search_select_ms of one merge
+                          of all lists into an empty search) and merge_wall_s (Searcher.merge, upload included), against
+                          python_merge_s: the same merge by grim.search.merge_hit_lists, a Python loop over the hits
 
     python tools/search_bench.py [--subjects N] [--steps K] [--warmup W] [--keep A,B,C,DQB1,DRB1] [--patients 8,64] [--top-n 10,256]
+                                 [--merge-lists 8]
 """
 import argparse
 import json
@@ -34,6 +39,7 @@ def main():
     ap.add_argument("--keep", default="A,B,C,DQB1,DRB1", help="locus names to keep, comma separated")
     ap.add_argument("--patients", default="8,64", help="patient counts, comma separated: the first N subjects")
     ap.add_argument("--top-n", default="10,256", help="hits per patient, comma separated")
+    ap.add_argument("--merge-lists", type=int, default=8, help="lists of the merge leg (0: no merge leg)")
     args = ap.parse_args()
 
     import numpy as np
@@ -76,6 +82,7 @@ def main():
     matcher = nat.Matcher(ctx, mask, n_alleles)
     searchers = {top: nat.Searcher(ctx, mask, n_alleles, top, 0.0) for top in tops}  # min_p0 0.0: every computed pair is a candidate
     out = {}
+    merge = None
     try:
         batch.run()
         res, rows = batch.results()
@@ -109,6 +116,35 @@ def main():
             for top, sr in searchers.items():
                 rec["top_n"][str(top)]["stats"] = sr.stats()
                 rec["top_n"][str(top)]["hits"] = int(sr.results()[1].sum())
+        if args.merge_lists > 0:  # (e): the last patient count, the largest top_n; the searcher's patients are still set
+            from grim.search import merge_hit_lists
+
+            n, top = counts[-1], max(tops)
+            sr = searchers[top]
+            whole = sr.results()
+            made = []
+            for part in range(args.merge_lists):  # the donors dealt round-robin: every list is full
+                sr.reset()
+                sr.run_records(res[part::args.merge_lists], rows, ids[part::args.merge_lists])
+                made.append(sr.results())
+            lists = (np.stack([m[0] for m in made]), np.stack([m[1] for m in made]))
+            leg = merge = {"lists": args.merge_lists, "patients": n, "top_n": top, "upload_bytes": lists[0].nbytes + lists[1].nbytes,
+                           "merge_select_ms": [], "merge_wall_s": [], "python_merge_s": []}
+            for step in range(args.warmup + args.steps):
+                sr.reset()
+                t0 = timeit.default_timer()
+                sr.merge(*lists)
+                wall = timeit.default_timer() - t0
+                if step >= args.warmup:
+                    leg["merge_wall_s"].append(wall)
+                    leg["merge_select_ms"].append(sr.select_ms())
+            got = sr.results()
+            leg["equals_one_run"] = bool(got[0].tobytes() == whole[0].tobytes() and got[1].tobytes() == whole[1].tobytes())
+            for step in range(min(3, args.steps)):  # the route it replaces: a Python loop over the hits (search_donors' last step)
+                t0 = timeit.default_timer()
+                twin = merge_hit_lists(made, top, 0.0)
+                leg["python_merge_s"].append(timeit.default_timer() - t0)
+            leg["python_equals_device"] = bool(twin[0].tobytes() == got[0].tobytes())
     finally:
         for sr in searchers.values():
             sr.close()
@@ -125,9 +161,11 @@ def main():
                 med(v)
 
     med(out)
+    if merge is not None:
+        med(merge)
     print(json.dumps({
         "workload": "pop4 graph, %d mixed subjects (seed 3) as donors, MR priors, keep %s, min_p0 0.0" % (args.subjects, "~".join(keep)),
-        "steps": args.steps, "warmup": args.warmup, "patients": out,
+        "steps": args.steps, "warmup": args.warmup, "patients": out, "merge": merge,
     }))
 
 
