@@ -181,18 +181,19 @@ def _accumulate_blocks(imputation, shared, lines, block_lines, acc, first=0):
     return spilled, kernel_ms, n_blocks
 
 
-def _counts_by_name(g, pops, table, spilled):
-    """an exported table (keys, pops, counts) and the spilled counts -> {pop: {haplotype: count}}"""
+def _counts_by_name(hap_name, pops, table, spilled):
+    """an exported table (keys, pops, counts) and the spilled counts -> {pop: {haplotype: count}}; hap_name: key -> the
+    haplotype's name (Graph.key_to_name); a population index beyond `pops` is named by its number"""
     keys, kpops, vals = table
     counts = {}
     names = {}
     for key, p, v in zip(keys.tolist(), kpops.tolist(), vals.tolist()):
         name = names.get(key)
         if name is None:
-            name = names[key] = "~".join(x for x in g.key_alleles(key) if x)
-        counts.setdefault(pops[p], {})[name] = v
+            name = names[key] = hap_name(key)
+        counts.setdefault(pops[p] if p < len(pops) else str(p), {})[name] = v
     for (p, name), v in spilled.items():
-        counts.setdefault(pops[p], {})[name] = v
+        counts.setdefault(pops[p] if p < len(pops) else str(p), {})[name] = v
     return counts
 
 
@@ -212,7 +213,7 @@ def m_step_counts(imputation, lines_or_path, config, block_lines=65536, planb=No
     acc = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(n_slots)], len(pops), first_capacity)
     try:
         spilled, kernel_ms, n_blocks = _accumulate_blocks(imputation, shared, lines, block_lines, acc)
-        counts = _counts_by_name(g, pops, acc.export(), spilled)
+        counts = _counts_by_name(g.key_to_name, pops, acc.export(), spilled)
         stats = acc.stats()
         stats.update(entries=acc.entries(), spill=acc.spill_count(), blocks=n_blocks, kernel_ms=kernel_ms)
     finally:
@@ -303,15 +304,20 @@ def chunk_text_lines(raw):
     return io.TextIOWrapper(io.BytesIO(raw), encoding="utf-8", newline=None).read().splitlines()
 
 
+def read_chunk(fh, offs, c):
+    """the bytes of chunk c of the file open (binary) as `fh`, `offs` being its chunk_offsets"""
+    fh.seek(offs[c])
+    return fh.read(offs[c + 1] - offs[c])
+
+
 def input_chunks(lines_or_path, chunk_lines):
     """(first input line, lines) of every chunk of `chunk_lines` lines.  A file is cut where grim.shard.chunk_offsets cuts it
-    for impute_sharded and m_step_sharded; a list by its index."""
+    for the sharded drivers, whose ranks read their chunks through the same `read_chunk`; a list by its index."""
     if isinstance(lines_or_path, (str, bytes, os.PathLike)):
         offs = nat.chunk_offsets(os.fspath(lines_or_path), chunk_lines)
         with open(lines_or_path, "rb") as fh:
             for c in range(len(offs) - 1):
-                fh.seek(offs[c])
-                yield c * chunk_lines, chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
+                yield c * chunk_lines, chunk_text_lines(read_chunk(fh, offs, c))
     else:
         lines = read_lines(lines_or_path)
         for lo in range(0, len(lines), chunk_lines):
@@ -353,7 +359,7 @@ def m_step_chunked(imputation, lines_or_path, config, chunk_lines, block_lines=6
         stats["entries"] = master.entries()
     finally:
         master.close()
-    return _counts_by_name(g, pops, table, spilled), stats, table
+    return _counts_by_name(g.key_to_name, pops, table, spilled), stats, table
 
 
 def write_freq_files(counts, freq_data_dir, pops):

@@ -1,5 +1,5 @@
 """
-Multi-GPU driver: one process per GPU, the subject file cut into fixed-size chunks of lines that the ranks PULL from a
+Multi-GPU drivers: one process per GPU, the subject file cut into fixed-size chunks of lines that the ranks PULL from a
 shared counter, graph replicated per GPU, NO collective on the data path.
 
 This is the split the reference's scripts/runfile_mp.py:109-148 intends (`split -l` + one worker per chunk + `cat` of the
@@ -7,34 +7,53 @@ per-chunk outputs), with three differences: workers are GPU ranks; chunks are ha
 varies by more than 1000x with its ambiguity, so equal line counts are not equal work -- SURVEY 8e); `.miss/.problem`
 keep the GLOBAL line index (the reference's per-chunk runs restart at 0).
 
-Data path of a rank: ONE long-lived streaming pipeline (grim_stream: tokenizer threads -> device -> formatter threads)
-for the whole job.  A pulled chunk is a byte range of the input file; its raw bytes go to the stream as one input SEGMENT
-(grim_stream_segment carries the chunk's global line index), so chunk k+1 is tokenised while chunk k is on the device -- no
-per-chunk stream, no Python line splitting.
+THE PROTOCOL (`_Job`, once for every driver).  The only communication is the control plane on the job's rendezvous
+store, and every key of a job carries the job's tag, a fresh id that rank 0 publishes:
+  - chunks: an atomic fetch-add on the store hands out the next chunk number (`_Job.chunks`); a chunk is a byte range of
+    the input file (`chunk_offsets`), read by the rank that pulled it;
+  - waits are POLLED and look at the other ranks' error slots (`_Control.wait_bytes`): a rank that waits for something
+    of a rank that failed stops with `_PeerFailed` instead of waiting for ever, or for the job's `timeout_s`;
+  - the body of the job runs guarded (`_Job.body`): whatever it raises is kept, the rank's own error is reported in its
+    error slot, the caller's clean-up runs;
+  - then every rank, failed or not, reaches the first barrier and reads the error slots (`_Job.closing`): it raises its
+    own error, else "<fn>: rank(s) [...] failed:" with the first report, else the peer failure it met; only when nobody
+    failed does rank 0's epilogue run;
+  - a second barrier ends the job on every path -- nobody leaves while another rank still reads the store -- and after it
+    every rank removes the blobs it published, collected or not;
+  - data on the store (`publish` / `collect` / `from_rank0`): bytes in pieces of at most PIECE_BYTES a key, framed by
+    `_pack` / `_unpack`; `from_rank0` is "rank 0 computes, every rank decodes the same bytes";
+  - `agree`: a short decision of rank 0's for every rank, its key removed once all have read it.
 
-Outputs are written ONCE, straight into the six final files, by every rank (no part files, no `cat`): as soon as a chunk
-is formatted its rank publishes the SIZES of its six pieces on the job's store; where chunk c's pieces begin is the sum of
-the sizes of the chunks before it, so only sizes wait for sizes -- a rank's placer thread picks them up and the stream's
-worker threads pwrite the formatted buffers at their final offsets (grim_stream_segment_wait / _place) while the pipeline
-is already busy with later chunks.
+WHAT EACH DRIVER ADDS
+`impute_sharded`: ONE long-lived streaming pipeline per rank (grim_stream: tokenizer threads -> device -> formatter
+threads) for the whole job.  A pulled chunk's raw bytes go to the stream as one input SEGMENT (grim_stream_segment carries
+the chunk's global line index), so chunk k+1 is tokenised while chunk k is on the device -- no per-chunk stream, no Python
+line splitting.  Outputs are written ONCE, straight into the six final files, by every rank (no part files, no `cat`): as
+soon as a chunk is formatted its rank publishes the SIZES of its six pieces on the store; where chunk c's pieces begin is
+the sum of the sizes of the chunks before it, so only sizes wait for sizes -- a rank's placer thread picks them up and the
+stream's worker threads pwrite the formatted buffers at their final offsets (grim_stream_segment_wait / _place) while the
+pipeline is already busy with later chunks.  Rank 0 makes the files first ("ok" / "failed" under the job's files key) and
+its epilogue checks their sizes and gathers the ranks' unsupported subjects.  Its waits have no deadline.
 
-The only communication is the control plane: an atomic fetch-add on the job's rendezvous store (the next chunk number),
-the job's id, six sizes per chunk, one barrier at the end, and an error slot per rank so that a rank that fails does not
-leave the others waiting.
+`m_step_sharded`, `em_fixed_support_sharded`: each chunk's count table is built in a fresh accumulator on the
+rank's GPU and published as bytes, rank 0 folds the tables in CHUNK order (EmAccumulator.merge_records) and every rank
+decodes the one result; the EM refreshes every rank's graph from it and agrees on when to stop.
 
-The M-step and the fixed-support EM shard the same way (`m_step_sharded`, `em_fixed_support_sharded`): ranks
-pull chunks, each chunk's count table is built in a fresh accumulator on the rank's GPU and published on the store as bytes,
-rank 0 folds the tables in CHUNK order (EmAccumulator.merge_records) and publishes the one result every rank returns.
+`search_sharded`, `search_file_sharded`: a rank's device accumulates hit lists across its chunks, ranks other
+than 0 publish theirs, rank 0 merges them on the device and every rank decodes the one answer; the file variant agrees on
+the outcome of rank 0's CSV.
 
 Launch:  torchrun --nproc-per-node N --master-addr 127.0.0.1 your_script.py   ->  impute_sharded(conf)
-(`impute_sharded` joins the job itself -- gloo, control plane only -- when the caller has not initialised
-torch.distributed; alone, without WORLD_SIZE > 1, it runs every chunk in this process).
+(a driver joins the job itself -- gloo, control plane only -- when the caller has not initialised torch.distributed;
+alone, without WORLD_SIZE > 1, it runs every chunk in this process and touches no store).
 """
 
+import contextlib
 import json
 import os
 import pathlib
 import queue
+import struct
 import threading
 import time
 import traceback
@@ -42,17 +61,13 @@ import uuid
 
 OUTPUT_KEYS = ("umug", "umug_pops", "pmug", "pmug_pops", "miss", "problem")
 DEFAULT_CHUNK_LINES = 65536
+PIECE_BYTES = 4 << 20  # the most one store key carries: the store's own value limit has not been measured
 
 
 def shard_range(n, rank, world):
     """[begin, end) of rank's contiguous block of ceil(n/world) lines (the static split of runfile_mp.py:113-124)."""
     per = -(-n // world) if world > 0 else n
     return min(n, rank * per), min(n, (rank + 1) * per)
-
-
-def merge_texts(per_rank):
-    """per_rank: list (rank order) of dicts of output texts -> one dict, rank order preserved."""
-    return {k: "".join(t.get(k, "") for t in per_rank) for k in OUTPUT_KEYS}
 
 
 def chunk_offsets(path, chunk_lines):
@@ -90,7 +105,6 @@ class _Control:
                 # process group at all)
                 os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
                 dist.init_process_group(backend="gloo")
-                self._own_group = True
             if dist.is_initialized():
                 self.dist = dist
                 self.rank, self.world = dist.get_rank(), dist.get_world_size()
@@ -190,13 +204,207 @@ class _Control:
             return False
 
 
+class _Job:
+    """One sharded call, on every rank: the protocol of the module docstring.  A driver is
+
+        job = _Job("<fn>", timeout_s, chunk_lines)
+        with job.body():        # this rank's work; job.cleanup takes what has to be closed whatever happens
+            for c, first_line, raw in job.chunks(in_path): ...
+        with job.closing():     # first barrier, raise if any rank failed ... last barrier, blobs removed
+            ...                 # what rank 0 does once every rank has done its work (job.close() when there is nothing)
+    """
+
+    def __init__(self, fn, timeout_s=None, chunk_lines=None):
+        """fn: the driver's name, for error texts; timeout_s: as `_Control`'s (None: waits without a deadline)"""
+        self.fn = fn
+        self.ctl = _Control(timeout_s)
+        self.rank, self.world = self.ctl.rank, self.ctl.world
+        self.chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
+        # the job's id: unique per call and per job, published by rank 0 (keys of an earlier job on the same store never match)
+        self.tag = self.ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
+        self.n_chunks = 0  # (known once `chunks` has begun)
+        self.cleanup = contextlib.ExitStack()  # runs when the body ends, however it ends
+        self.error = self.peer_failed = None
+        self.published = []  # every store key of this rank's blobs
+        self.agreed = 0
+
+    # ---- the guarded stages ---------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def body(self):
+        """the rank's work: the other ranks must not wait for this one forever, so nothing it raises leaves here -- it is
+        kept for `closing`, and the rank's own error goes into its error slot"""
+        try:
+            with self.cleanup:
+                yield
+        except BaseException as e:  # noqa: B902  (raised again by `closing`, behind the barrier)
+            if isinstance(e, _PeerFailed):
+                self.peer_failed = e  # not this rank's failure: the barrier's error list names the rank whose it is
+            else:
+                self.error = e
+                self.ctl.report_error(self.tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
+
+    @contextlib.contextmanager
+    def closing(self):
+        """the barrier every rank reaches, then: this rank's own error, else the report of the ranks that failed, else the
+        peer failure it met, else the `with` block (the epilogue).  One more barrier on every path: nobody leaves while
+        another rank still reads the store; after it the rank's blobs go"""
+        try:
+            failed = self.ctl.barrier_and_errors(self.tag)
+            if self.error is not None:
+                raise self.error
+            if failed:
+                raise RuntimeError("%s: rank(s) %s failed:\n%s" % (self.fn, [r for r, _ in failed], failed[0][1]))
+            if self.peer_failed is not None:
+                raise self.peer_failed
+            yield
+        finally:
+            self.ctl.barrier()
+            for key in self.published:  # (collected or not: after a failure nobody will ask for them)
+                self.ctl.delete(key)
+
+    def close(self):
+        with self.closing():
+            pass
+
+    # ---- chunks and the rank's device ------------------------------------------------------------------------------------
+    def chunks(self, in_path):
+        """(c, first line, raw bytes) of every chunk of the file this rank pulls from the job's counter"""
+        from .em import read_chunk
+
+        offs = chunk_offsets(in_path, self.chunk_lines)
+        self.n_chunks = len(offs) - 1
+        with open(in_path, "rb") as fh:
+            while True:
+                c = self.ctl.next_chunk(self.tag)
+                if c >= self.n_chunks:
+                    return
+                yield c, c * self.chunk_lines, read_chunk(fh, offs, c)
+
+    def imputation(self, config, graph=None):
+        """the rank's Imputation on device LOCAL_RANK % device count; the graph is built from the configuration's files
+        when none is given"""
+        from . import _native as nat
+        from .imputation.impute import Imputation
+        from .imputation.networkx_graph import Graph
+
+        if graph is None:
+            graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
+        return Imputation(graph, config, device=self.ctl.local % max(1, nat.lib().grim_device_count()))
+
+    # ---- data on the store ---------------------------------------------------------------------------------------------
+    def publish(self, name, blob):
+        """blob under `name`: pieces of at most PIECE_BYTES, then the head key that says how many (set last: who sees it
+        finds every piece).  -> the store keys it set"""
+        n = max(1, -(-len(blob) // PIECE_BYTES))
+        keys = ["%s_%d" % (name, i) for i in range(n)] + [name]
+        self.published += keys
+        for i, key in enumerate(keys[:n]):
+            self.ctl.set(key, blob[i * PIECE_BYTES:(i + 1) * PIECE_BYTES])
+        self.ctl.set(name, str(n))
+        return keys
+
+    def collect(self, name, delete):
+        """the blob some rank publishes under `name`; delete: nobody else will ask for it"""
+        n = int(self.ctl.wait_key(name, self.tag))
+        blob = b"".join(self.ctl.wait_bytes("%s_%d" % (name, i), self.tag) for i in range(n))
+        if delete:
+            for i in range(n):
+                self.ctl.delete("%s_%d" % (name, i))
+            self.ctl.delete(name)
+        return blob
+
+    def from_rank0(self, name, make_blob):
+        """rank 0's make_blob() on every rank, so that all decode the same bytes (alone: no store traffic)"""
+        if self.rank != 0:
+            return self.collect(name, False)
+        blob = make_blob()
+        if self.world > 1:
+            self.publish(name, blob)
+        return blob
+
+    def agree(self, make_text):
+        """rank 0's make_text() on every rank: a short decision.  Its key is removed once every rank has read it"""
+        self.agreed += 1
+        key = "grim_agree_%s_%d" % (self.tag, self.agreed)
+        text = self.ctl.share(key, make_text)
+        self.ctl.barrier()  # every rank has read the key
+        if self.rank == 0:
+            self.ctl.delete(key)
+        return text
+
+
+# ---- the blob frame: a <Q head length, the JSON head, the arrays' bytes in order --------------------------------------------
+def _pack(head, arrays):
+    head = json.dumps(head).encode()
+    return struct.pack("<Q", len(head)) + head + b"".join(a.tobytes() for a in arrays)
+
+
+def _unpack(blob, specs, who):
+    """-> (head, arrays as copies); specs: per array (dtype, its number of items as a function of the head); who: the
+    driver named by the RuntimeError a blob of the wrong size ends in"""
+    import numpy as np
+
+    try:
+        (n_head,) = struct.unpack_from("<Q", blob, 0)
+        head = json.loads(blob[8:8 + n_head].decode())
+        shapes = [(np.dtype(dtype), int(count(head))) for dtype, count in specs]
+        size = 8 + n_head + sum(dtype.itemsize * n for dtype, n in shapes)
+    except (struct.error, ValueError, LookupError, TypeError):  # (cut inside the head, or not a head of this kind)
+        size = None
+    if size != len(blob):
+        raise RuntimeError("%s: a blob of %d bytes whose head asks for %s" % (who, len(blob), size))
+    arrays, at = [], 8 + n_head
+    for dtype, n in shapes:
+        arrays.append(np.frombuffer(blob, dtype=dtype, count=n, offset=at).copy())
+        at += dtype.itemsize * n
+    return head, arrays
+
+
+def _pack_table(keys, pops, counts, spilled, stats, unsupported):
+    """a chunk's (or the job's) count table as bytes; floats of the head as hex: every bit travels"""
+    import numpy as np
+
+    arrays = [np.ascontiguousarray(a, dtype=dt) for a, dt in ((keys, "<u8"), (pops, "<u4"), (counts, "<f8"))]
+    return _pack({"n": int(arrays[0].shape[0]), "stats": stats, "unsupported": [list(u) for u in unsupported],
+                  "spilled": [[int(p), name, float(v).hex()] for (p, name), v in spilled.items()]}, arrays)
+
+
+def _unpack_table(blob):
+    head, (keys, pops, counts) = _unpack(blob, [(dt, lambda h: h["n"]) for dt in ("<u8", "<u4", "<f8")], "m_step_sharded")
+    spilled = {(int(p), name): float.fromhex(v) for p, name, v in head["spilled"]}  # (insertion order = the sender's)
+    return keys, pops, counts, spilled, head["stats"], [tuple(u) for u in head["unsupported"]]
+
+
+def _pack_hits(patient_ok, hits, n_hits, stats, unsupported):
+    """a rank's (or the job's) hit lists as bytes (Python writes a float of the head so that it reads back the same)"""
+    import numpy as np
+
+    from . import _native as nat
+
+    hits = np.ascontiguousarray(hits, dtype=nat.SEARCH_DT)
+    return _pack({"patients": int(hits.shape[0]), "top_n": int(hits.shape[1]), "ok": [int(x) for x in patient_ok], "stats": stats,
+                  "unsupported": [list(u) for u in unsupported]}, [hits, np.ascontiguousarray(n_hits, dtype="<u4")])
+
+
+def _unpack_hits(blob):
+    import numpy as np
+
+    from . import _native as nat
+
+    head, (hits, n_hits) = _unpack(blob, [(nat.SEARCH_DT, lambda h: h["patients"] * h["top_n"]), ("<u4", lambda h: h["patients"])],
+                                   "search_sharded")
+    return (np.array(head["ok"], dtype=bool), hits.reshape(head["patients"], head["top_n"]), n_hits, head["stats"],
+            [tuple(u) for u in head["unsupported"]])
+
+
+# ---- impute: one stream per rank, every rank writes its pieces into the six final files ------------------------------------
 class _Placement:
     """where chunk c's piece of each output file begins: the sum of the sizes of the chunks before it, whoever ran them.
     Sizes travel through the job's store (one key per chunk, set once); a rank asks in increasing chunk order, so its
     running prefix only ever moves forward."""
 
-    def __init__(self, ctl, tag):
-        self.ctl, self.tag = ctl, tag
+    def __init__(self, job):
+        self.ctl, self.tag = job.ctl, job.tag
         self.own = {}
         self.upto, self.prefix = 0, [0] * 6
 
@@ -359,26 +567,26 @@ def impute_sharded(conf_file, hap_pop_pair=False, graph=None, compute=None, proj
     from .run_impute_def import load_config
     from .imputation.impute import Imputation as _I, UnsupportedSubjects
 
-    ctl = _Control()
-    chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
+    job = _Job("impute_sharded", None, chunk_lines)  # (waits without a deadline)
+    ctl, tag = job.ctl, job.tag
     names = {key: (path_key, flag) for key, path_key, flag in _I._OUT_FILES}
-    error = peer_failed = None
-    sink = unlinker = None
-    files_announced = False
-    alone = ctl.world == 1  # the one rank's stream appends to the output files: nothing to place
-    # the job's id: unique per call and per job, published by rank 0 (keys of an earlier job on the same store never match)
-    tag = ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
+    alone = job.world == 1  # the one rank's stream appends to the output files: nothing to place
     files_key = "grim_files_" + tag
-    config = flags = None
-    n_chunks = 0
-    placement = None if alone else _Placement(ctl, tag)
+    files_announced = False
+    placement = None if alone else _Placement(job)
     unsupported = []
-    try:
+    result = None
+
+    def files_failed():  # (the other ranks wait for files_key)
+        if job.rank == 0 and not alone and not files_announced:
+            ctl.set(files_key, "failed")
+
+    with job.body():
+        job.cleanup.callback(files_failed)
         config, out_dir = load_config(conf_file, project_dir_graph, project_dir_in_file)
-        in_path = config["imputation_input_file"]
         flags = {k: (names[k][1] is None or bool(config[names[k][1]])) for k in OUTPUT_KEYS}
         out_paths = {k: config[names[k][0]] for k in OUTPUT_KEYS}
-        if ctl.rank == 0:
+        if job.rank == 0:
             pathlib.Path(out_dir).mkdir(parents=False, exist_ok=True)
             if not alone:
                 # the shared output files: made by rank 0 before any rank opens them for its pieces.  An earlier run's file
@@ -397,154 +605,50 @@ def impute_sharded(conf_file, hap_pop_pair=False, graph=None, compute=None, proj
                 if stale:
                     unlinker = threading.Thread(target=lambda: [os.unlink(f) for f in stale], name="grim-unlink", daemon=True)
                     unlinker.start()
+                    job.cleanup.callback(unlinker.join)
         elif ctl.wait_key(files_key, tag) != "ok":
             raise RuntimeError("impute_sharded: rank 0 could not create the output files")
-        offs = chunk_offsets(in_path, chunk_lines)
-        n_chunks = len(offs) - 1
         if compute is None:
-            from .imputation.networkx_graph import Graph
-            from . import _native as nat
-
-            if graph is None:
-                graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
-            n_dev = max(1, nat.lib().grim_device_count())
-            imp = _I(graph, config, device=ctl.local % n_dev)
+            imp = job.imputation(config, graph)
             sink = _StreamSink(imp, config, hap_pop_pair, out_paths, flags, placement)
         else:
             imp = None
             sink = _ComputeSink(compute, config, out_paths, flags, placement)
-        with open(in_path, "rb") as fh:
-            while True:
-                c = ctl.next_chunk(tag)
-                if c >= n_chunks:
-                    break
-                fh.seek(offs[c])
-                sink.feed(fh.read(offs[c + 1] - offs[c]), c * chunk_lines, c)
+        job.cleanup.callback(sink.abort)
+        for c, first, raw in job.chunks(config["imputation_input_file"]):
+            sink.feed(raw, first, c)
         sink.finish()
-        sink = None
         # subjects the device could not take: the single-GPU path raises unless told to skip them, so does every rank here
         unsupported = list(imp.unsupported) if imp is not None else []
         if unsupported and imp.on_unsupported == "raise":
             raise UnsupportedSubjects(unsupported)
-        ctl.set("grim_unsup_%s_%d" % (tag, ctl.rank), json.dumps(unsupported))
-    except BaseException as e:  # the other ranks must not wait for this one forever: report, reach the barrier, raise
-        if sink is not None:
-            sink.abort()
-        if isinstance(e, _PeerFailed):
-            peer_failed = e  # not this rank's failure: the barrier's error list names the rank whose it is
-        else:
-            error = e
-            ctl.report_error(tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
-        if ctl.rank == 0 and not alone and not files_announced:
-            ctl.set(files_key, "failed")
-    failed = ctl.barrier_and_errors(tag)
-    result = None
-    try:
-        if error is not None:
-            raise error
-        if failed:
-            raise RuntimeError("impute_sharded: rank(s) %s failed:\n%s" % ([r for r, _ in failed], failed[0][1]))
-        if peer_failed is not None:
-            raise peer_failed
-        if ctl.rank == 0:
+        ctl.set("grim_unsup_%s_%d" % (tag, job.rank), json.dumps(unsupported))
+    with job.closing():
+        if job.rank == 0:
             if not alone:
-                total = placement.base(n_chunks)  # every size is on the store by now
+                total = placement.base(job.n_chunks)  # every size is on the store by now
                 for ki, k in enumerate(OUTPUT_KEYS):
                     if flags[k] and os.path.getsize(out_paths[k]) != total[ki]:
                         raise RuntimeError("impute_sharded: %s holds %d bytes, the chunks add up to %d" % (
                             out_paths[k], os.path.getsize(out_paths[k]), total[ki]))
-                for r in range(1, ctl.world):
+                for r in range(1, job.world):
                     unsupported += [tuple(u) for u in json.loads(ctl.wait_key("grim_unsup_%s_%d" % (tag, r), tag))]
                 unsupported.sort(key=lambda u: u[0])
             result = {"unsupported": [tuple(u) for u in unsupported]}
             for k in OUTPUT_KEYS:
-                path_key, _ = names[k]
                 if not flags[k]:
                     result[k] = "" if return_texts else None
                 elif not return_texts:
-                    result[k] = config[path_key]
-    finally:
-        if unlinker is not None:
-            unlinker.join()
-        ctl.barrier()  # one barrier at the end on every path: nobody leaves while another rank still reads the store
-    if ctl.rank == 0 and return_texts and result is not None:
+                    result[k] = out_paths[k]
+    if result is not None and return_texts:
         for k in OUTPUT_KEYS:
             if flags[k]:
-                with open(config[names[k][0]]) as fh:
+                with open(out_paths[k]) as fh:
                     result[k] = fh.read()
     return result
 
 
 # ---- the sharded M-step: every chunk's table onto the store, folded by rank 0 in chunk order ---------------------
-PIECE_BYTES = 4 << 20  # the most one store key carries: the store's own value limit has not been measured
-
-
-def _pack_table(keys, pops, counts, spilled, stats, unsupported):
-    """a chunk's (or the job's) result as bytes: a JSON head (floats as hex: every bit travels) and the three arrays"""
-    import struct
-
-    import numpy as np
-
-    keys = np.ascontiguousarray(keys, dtype="<u8")
-    pops = np.ascontiguousarray(pops, dtype="<u4")
-    counts = np.ascontiguousarray(counts, dtype="<f8")
-    head = json.dumps({"n": int(keys.shape[0]), "stats": stats, "unsupported": [list(u) for u in unsupported],
-                       "spilled": [[int(p), name, float(v).hex()] for (p, name), v in spilled.items()]}).encode()
-    return struct.pack("<Q", len(head)) + head + keys.tobytes() + pops.tobytes() + counts.tobytes()
-
-
-def _unpack_table(blob):
-    import struct
-
-    import numpy as np
-
-    (n_head,) = struct.unpack_from("<Q", blob, 0)
-    head = json.loads(blob[8:8 + n_head].decode())
-    n, at = head["n"], 8 + n_head
-    if len(blob) != at + 20 * n:
-        raise RuntimeError("m_step_sharded: a table of %d entries in %d bytes" % (n, len(blob) - at))
-    keys = np.frombuffer(blob, dtype="<u8", count=n, offset=at).copy()
-    pops = np.frombuffer(blob, dtype="<u4", count=n, offset=at + 8 * n).copy()
-    counts = np.frombuffer(blob, dtype="<f8", count=n, offset=at + 12 * n).copy()
-    spilled = {(int(p), name): float.fromhex(v) for p, name, v in head["spilled"]}  # (insertion order = the sender's)
-    return keys, pops, counts, spilled, head["stats"], [tuple(u) for u in head["unsupported"]]
-
-
-def _publish(ctl, name, blob):
-    """blob under `name`: pieces of at most PIECE_BYTES, then the head key that says how many (set last: who sees it finds
-    every piece)"""
-    n = max(1, -(-len(blob) // PIECE_BYTES))
-    for i in range(n):
-        ctl.set("%s_%d" % (name, i), blob[i * PIECE_BYTES:(i + 1) * PIECE_BYTES])
-    ctl.set(name, str(n))
-
-
-def _collect(ctl, name, tag, delete):
-    n = int(ctl.wait_key(name, tag))
-    blob = b"".join(ctl.wait_bytes("%s_%d" % (name, i), tag) for i in range(n))
-    if delete:
-        for i in range(n):
-            ctl.delete("%s_%d" % (name, i))
-        ctl.delete(name)
-    return blob
-
-
-def _names_of(keys, pops, counts, spilled, pop_names, hap_name):
-    out = {}
-    names = {}
-    for key, p, v in zip(keys.tolist(), pops.tolist(), counts.tolist()):
-        name = names.get(key)
-        if name is None:
-            name = names[key] = hap_name(key)
-        out.setdefault(pop_names[p] if p < len(pop_names) else str(p), {})[name] = v
-    for (p, name), v in spilled.items():
-        out.setdefault(pop_names[p] if p < len(pop_names) else str(p), {})[name] = v
-    return out
-
-
-M_STEP_SUMS = ("subjects_used", "skipped_plan_c", "contributions", "rehashes", "spill", "blocks", "kernel_ms")
-
-
 def m_step_sharded(conf_file, chunk_lines=None, graph=None, compute=None, timeout_s=1800, block_lines=65536):
     """The M-step across the ranks of the torch.distributed job (or alone if there is none), by the chunk-ordered contract
     of DESIGN 4.5: the input is cut into chunks of `chunk_lines` lines as `impute_sharded` cuts it, the ranks pull chunk
@@ -560,133 +664,80 @@ def m_step_sharded(conf_file, chunk_lines=None, graph=None, compute=None, timeou
     `compute(config, lines, line_offset) -> (keys, pops, counts, spilled, stats)` can be injected (tests); the fold then
     runs through grim.em.fold_chunk_tables and haplotypes are named by their key.  Every wait ends `timeout_s` seconds
     after the call began at the latest, or when a peer reports an error; every rank raises when any rank failed."""
-    return _m_step_sharded(conf_file, chunk_lines, graph, compute, timeout_s, block_lines, None)
+    return _m_step_sharded(_Job("m_step_sharded", timeout_s, chunk_lines), conf_file, graph, compute, block_lines, {})
 
 
-def _m_step_sharded(conf_file, chunk_lines, graph, compute, timeout_s, block_lines, _state):
-    """m_step_sharded; `_state`: a dict that keeps the rank's Imputation (and with it its device graph) from call to call"""
-    from .em import chunk_text_lines
+def _m_step_sharded(job, conf_file, graph, compute, block_lines, state):
+    """m_step_sharded as `job`; `state`: a dict that keeps the rank's Imputation (and with it its device graph) from call to
+    call"""
+    from . import em
     from .run_impute_def import load_config
 
-    ctl = _Control(timeout_s)
-    chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
-    error = peer_failed = None
     result = None
-    tag = ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
-    master = None
-    try:
+    with job.body():
         config, _ = load_config(conf_file)
-        in_path = config["imputation_input_file"]
-        offs = chunk_offsets(in_path, chunk_lines)
-        n_chunks = len(offs) - 1
         imp = shared = None
+        pop_names, hap_name = list(config.get("pops") or []), str
         if compute is None:
             from . import _native as nat
             from .blocks import Blocks
-            from .em import chunk_table
-            from .imputation.impute import Imputation as _I
-            from .imputation.networkx_graph import Graph
 
-            if _state is not None and _state.get("imp") is not None:
-                imp = _state["imp"]
-            else:
-                if graph is None:
-                    graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
-                n_dev = max(1, nat.lib().grim_device_count())
-                imp = _I(graph, config, device=ctl.local % n_dev)
-                if _state is not None:
-                    _state["imp"] = imp
+            imp = state.get("imp")
+            if imp is None:
+                imp = state["imp"] = job.imputation(config, graph)
             shared = Blocks(imp, config, None, True, True, output_haplotypes=True)
-            pop_names = list(imp.populations)
-            hap_name = imp.netGraph.key_to_name
-        else:
-            pop_names = list(config.get("pops") or [])
-            hap_name = str
-        # ---- this rank's chunks ----------------------------------------------------------------------------------------
-        own = {}
-        with open(in_path, "rb") as fh:
-            while True:
-                c = ctl.next_chunk(tag)
-                if c >= n_chunks:
-                    break
-                fh.seek(offs[c])
-                lines = chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
-                if compute is None:
-                    acc, spilled, stats, bad = chunk_table(imp, shared, lines, c * chunk_lines, block_lines)
-                    try:
-                        keys, pops, counts = acc.export()
-                    finally:
-                        acc.close()
-                else:
-                    keys, pops, counts, spilled, stats = compute(config, lines, c * chunk_lines)
-                    bad = []
-                if ctl.rank == 0:
-                    own[c] = (keys, pops, counts, spilled, stats, bad)
-                else:
-                    _publish(ctl, "grim_emt_%s_%d" % (tag, c), _pack_table(keys, pops, counts, spilled, stats, bad))
-        # ---- rank 0: the fold, in chunk order --------------------------------------------------------------------------
-        final = "grim_emf_" + tag
-        if ctl.rank == 0:
-            from .em import fold_chunk_tables, fold_spilled
+            pop_names, hap_name = list(imp.populations), imp.netGraph.key_to_name
+        own = {}  # rank 0 keeps its chunks' tables, the other ranks publish theirs
+        for c, first, raw in job.chunks(config["imputation_input_file"]):
+            lines = em.chunk_text_lines(raw)
+            if compute is None:
+                acc, spilled, stats, bad = em.chunk_table(imp, shared, lines, first, block_lines)
+                try:
+                    keys, pops, counts = acc.export()
+                finally:
+                    acc.close()
+            else:
+                keys, pops, counts, spilled, stats = compute(config, lines, first)
+                bad = []
+            if job.rank == 0:
+                own[c] = (keys, pops, counts, spilled, stats, bad)
+            else:
+                job.publish("grim_emt_%s_%d" % (job.tag, c), _pack_table(keys, pops, counts, spilled, stats, bad))
 
-            stats = dict.fromkeys(M_STEP_SUMS, 0)
-            stats.update(kernel_ms=0.0, merge_ms=0.0, chunks=n_chunks)
-            spilled, unsupported, tables = {}, [], []
+        def fold():  # rank 0: the chunks' tables in chunk order -> the job's result as bytes
+            stats = dict.fromkeys(em.CHUNK_STATS, 0)
+            stats.update(kernel_ms=0.0, merge_ms=0.0, chunks=job.n_chunks)
+            spilled, unsupported, tables, master = {}, [], [], None
             if compute is None:
                 g = imp.netGraph
                 master = nat.EmAccumulator(shared.ctx, [g.adict.count(s) for s in range(len(g.full_loci))], len(pop_names))
-            for c in range(n_chunks):
+                job.cleanup.callback(master.close)
+            for c in range(job.n_chunks):
                 part = own.pop(c, None)
                 if part is None:
-                    part = _unpack_table(_collect(ctl, "grim_emt_%s_%d" % (tag, c), tag, True))
+                    part = _unpack_table(job.collect("grim_emt_%s_%d" % (job.tag, c), True))
                 keys, pops, counts, chunk_spilled, chunk_stats, bad = part
                 if master is not None:
                     master.merge_records(keys, pops, counts)
                     stats["merge_ms"] += master.merge_ms()
                 else:
                     tables.append((keys, pops, counts))
-                fold_spilled(spilled, chunk_spilled)
-                for k in M_STEP_SUMS:
+                em.fold_spilled(spilled, chunk_spilled)
+                for k in em.CHUNK_STATS:
                     stats[k] += chunk_stats.get(k, 0)
                 unsupported += bad
             if master is not None:
                 table = master.export()
                 stats["rehashes"] += master.stats()["rehashes"]
             else:
-                table = fold_chunk_tables(tables)
+                table = em.fold_chunk_tables(tables)
             stats["entries"] = int(table[0].shape[0])
-            blob = _pack_table(table[0], table[1], table[2], spilled, stats, sorted(unsupported))
-            if ctl.world > 1:
-                _publish(ctl, final, blob)
-        else:
-            blob = _collect(ctl, final, tag, False)
-        keys, pops, counts, spilled, stats, unsupported = _unpack_table(blob)  # every rank reads the same bytes
+            return _pack_table(table[0], table[1], table[2], spilled, stats, sorted(unsupported))
+
+        keys, pops, counts, spilled, stats, unsupported = _unpack_table(job.from_rank0("grim_emf_" + job.tag, fold))
         stats["unsupported"] = unsupported
-        result = (_names_of(keys, pops, counts, spilled, pop_names, hap_name), stats, (keys, pops, counts))
-    except BaseException as e:  # the other ranks must not wait for this one: report, reach the barrier, raise
-        if isinstance(e, _PeerFailed):
-            peer_failed = e
-        else:
-            error = e
-            ctl.report_error(tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
-    finally:
-        if master is not None:
-            master.close()
-    failed = ctl.barrier_and_errors(tag)
-    try:
-        if error is not None:
-            raise error
-        if failed:
-            raise RuntimeError("m_step_sharded: rank(s) %s failed:\n%s" % ([r for r, _ in failed], failed[0][1]))
-        if peer_failed is not None:
-            raise peer_failed
-    finally:
-        ctl.barrier()  # nobody leaves while another rank still reads the store
-        if ctl.rank == 0 and ctl.world > 1 and result is not None:
-            n = max(1, -(-len(blob) // PIECE_BYTES))
-            for i in range(n):
-                ctl.delete("grim_emf_%s_%d" % (tag, i))
-            ctl.delete("grim_emf_" + tag)
+        result = (em._counts_by_name(hap_name, pop_names, (keys, pops, counts), spilled), stats, (keys, pops, counts))
+    job.close()
     return result
 
 
@@ -699,17 +750,17 @@ def em_fixed_support_sharded(conf_file, iterations, chunk_lines=None, tol=None, 
     `unsupported`, the same on every rank apart from `refresh_ms`."""
     from . import _native as nat
 
-    state = {"imp": None}  # one Imputation, and with it one device graph, for every iteration
+    state = {}  # one Imputation, and with it one device graph, for every iteration
     out = []
     for _ in range(int(iterations)):
-        _, it, table = _m_step_sharded(conf_file, chunk_lines, graph, None, timeout_s, block_lines, state)
-        ctl, imp = _Control(timeout_s), state["imp"]
+        job = _Job("m_step_sharded", timeout_s, chunk_lines)
+        _, it, table = _m_step_sharded(job, conf_file, graph, None, block_lines, state)
+        imp = state["imp"]
         rs = imp.netGraph.refresh(nat.default_context(imp.device), table)
         it.update(total=rs["total"], delta=rs["delta"], matched=rs["matched"], zero_full=rs["zero_full"], n_full=rs["n_full"],
                   outside=it["entries"] - rs["matched"], refresh_ms=rs["kernel_ms"])
         out.append(it)
-        stop = ctl.share("grim_emstop_%d" % _next_call(), lambda: "1" if tol is not None and rs["delta"] <= tol else "0")
-        if stop == "1":
+        if job.agree(lambda: "1" if tol is not None and rs["delta"] <= tol else "0") == "1":
             break
     return out
 
@@ -717,40 +768,6 @@ def em_fixed_support_sharded(conf_file, iterations, chunk_lines=None, tol=None, 
 # ---- the sharded donor search: every rank's hit lists onto the store, merged by rank 0 on the device ----------------
 SEARCH_SUMS = ("donors_valid", "donors_private", "pairs", "row_pairs", "candidates", "host_pairs", "kernel_ms", "select_ms", "blocks",
                "download_bytes")
-
-
-def _pack_hits(patient_ok, hits, n_hits, stats, unsupported):
-    """a rank's (or the job's) hit lists as bytes: a JSON head (Python writes a float so that it reads back the same) and the
-    raw hits / n_hits bytes"""
-    import struct
-
-    import numpy as np
-
-    from . import _native as nat
-
-    hits = np.ascontiguousarray(hits, dtype=nat.SEARCH_DT)
-    n_hits = np.ascontiguousarray(n_hits, dtype="<u4")
-    head = json.dumps({"patients": int(hits.shape[0]), "top_n": int(hits.shape[1]), "ok": [int(x) for x in patient_ok], "stats": stats,
-                       "unsupported": [list(u) for u in unsupported]}).encode()
-    return struct.pack("<Q", len(head)) + head + hits.tobytes() + n_hits.tobytes()
-
-
-def _unpack_hits(blob):
-    import struct
-
-    import numpy as np
-
-    from . import _native as nat
-
-    (n_head,) = struct.unpack_from("<Q", blob, 0)
-    head = json.loads(blob[8:8 + n_head].decode())
-    n_p, top_n, at = head["patients"], head["top_n"], 8 + n_head
-    size = nat.SEARCH_DT.itemsize * n_p * top_n
-    if len(blob) != at + size + 4 * n_p:
-        raise RuntimeError("search_sharded: hit lists of %d patients x %d in %d bytes" % (n_p, top_n, len(blob) - at))
-    hits = np.frombuffer(blob, dtype=nat.SEARCH_DT, count=n_p * top_n, offset=at).reshape(n_p, top_n).copy()
-    n_hits = np.frombuffer(blob, dtype="<u4", count=n_p, offset=at + size).copy()
-    return np.array(head["ok"], dtype=bool), hits, n_hits, head["stats"], [tuple(u) for u in head["unsupported"]]
 
 
 def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk_lines=None, graph=None, compute=None, timeout_s=1800,
@@ -772,58 +789,46 @@ def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk
     `compute(config, patient_lines, donor_lines, first) -> (hits, n_hits, stats)` can be injected (tests): a rank then folds
     its chunks' lists, and rank 0 the ranks' lists, with grim.search.merge_hit_lists.  Every wait ends `timeout_s` seconds
     after the call began at the latest, or when a peer reports an error; every rank raises when any rank failed."""
+    from .search import _check
+
+    top_n, min_p0 = _check(top_n, min_p0)
+    return _search_sharded(_Job("search_sharded", timeout_s, chunk_lines), conf_file, patients_path, keep_loci, top_n, min_p0, graph,
+                           compute, block_lines)
+
+
+def _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, compute, block_lines):
+    """search_sharded as `job`, top_n and min_p0 checked"""
     import numpy as np
 
     from .blocks import read_lines
     from .em import chunk_text_lines
     from .run_impute_def import load_config
-    from .search import _check, _empty_hits, merge_hit_lists
+    from .search import _empty_hits, merge_hit_lists
 
-    top_n, min_p0 = _check(top_n, min_p0)
-    ctl = _Control(timeout_s)
-    chunk_lines = int(chunk_lines or os.environ.get("GRIM_SHARD_LINES", DEFAULT_CHUNK_LINES))
-    error = peer_failed = None
-    result = blob = None
-    tag = ctl.share("grim_job_%d" % _next_call(), lambda: uuid.uuid4().hex[:12])
-    search = None
-    try:
+    result = None
+    with job.body():
         config, _ = load_config(conf_file)
-        in_path = config["imputation_input_file"]
-        offs = chunk_offsets(in_path, chunk_lines)
-        n_chunks = len(offs) - 1
         plines = read_lines(patients_path)
-        imp = None
         patients_bad = []
         if compute is None:
-            from . import _native as nat
-            from .imputation.impute import Imputation as _I
-            from .imputation.networkx_graph import Graph
             from .search import DonorSearch
 
-            if graph is None:
-                graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
-            n_dev = max(1, nat.lib().grim_device_count())
-            imp = _I(graph, config, device=ctl.local % n_dev)
+            imp = job.imputation(config, graph)
             search = DonorSearch(imp, plines, config, keep_loci, top_n, min_p0, block_lines)
+            job.cleanup.callback(search.close)
             patients_bad = list(imp.unsupported)
         else:
             running = (_empty_hits(len(plines), top_n), np.zeros(len(plines), dtype=np.uint32))
             sums = dict.fromkeys(SEARCH_SUMS, 0)
-        # ---- this rank's chunks ----------------------------------------------------------------------------------------
-        with open(in_path, "rb") as fh:
-            while True:
-                c = ctl.next_chunk(tag)
-                if c >= n_chunks:
-                    break
-                fh.seek(offs[c])
-                lines = chunk_text_lines(fh.read(offs[c + 1] - offs[c]))
-                if compute is None:
-                    search.feed(lines, first=c * chunk_lines)
-                else:
-                    hits, n_hits, chunk_stats = compute(config, plines, lines, c * chunk_lines)
-                    running = merge_hit_lists([(hits, n_hits)], top_n, min_p0, running=running)
-                    for k in SEARCH_SUMS:
-                        sums[k] += chunk_stats.get(k, 0)
+        for c, first, raw in job.chunks(config["imputation_input_file"]):
+            lines = chunk_text_lines(raw)
+            if compute is None:
+                search.feed(lines, first=first)
+            else:
+                hits, n_hits, chunk_stats = compute(config, plines, lines, first)
+                running = merge_hit_lists([(hits, n_hits)], top_n, min_p0, running=running)
+                for k in SEARCH_SUMS:
+                    sums[k] += chunk_stats.get(k, 0)
 
         def mine():
             if compute is None:
@@ -831,13 +836,8 @@ def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk
                 return ok, hits, n_hits, stats, imp.unsupported[len(patients_bad):]
             return np.ones(len(plines), dtype=bool), running[0], running[1], dict(sums), []
 
-        # ---- ranks other than 0 publish their lists; rank 0 merges them into its own -----------------------------------
-        final = "grim_srf_" + tag
-        if ctl.rank != 0:
-            _publish(ctl, "grim_srl_%s_%d" % (tag, ctl.rank), _pack_hits(*mine()))
-            blob = _collect(ctl, final, tag, False)
-        else:
-            others = [_unpack_hits(_collect(ctl, "grim_srl_%s_%d" % (tag, r), tag, True)) for r in range(1, ctl.world)]
+        def merged():  # rank 0: the other ranks' lists merged into its own -> the job's answer as bytes
+            others = [_unpack_hits(job.collect("grim_srl_%s_%d" % (job.tag, r), True)) for r in range(1, job.world)]
             for r, part in enumerate(others):
                 if part[1].shape != (len(plines), top_n):
                     raise RuntimeError("search_sharded: rank %d sent lists of shape %r" % (r + 1, part[1].shape))
@@ -855,49 +855,17 @@ def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk
                 for k in SEARCH_SUMS:
                     stats[k] = stats.get(k, 0) + part[3].get(k, 0)
                 unsupported += part[4]
-            stats.update(chunks=n_chunks, merge_ms=merge_ms, patients_unsupported=[list(u) for u in patients_bad])
-            blob = _pack_hits(ok, hits, n_hits, stats, sorted(unsupported))
-            if ctl.world > 1:
-                _publish(ctl, final, blob)
-        ok, hits, n_hits, stats, unsupported = _unpack_hits(blob)  # every rank reads the same bytes
+            stats.update(chunks=job.n_chunks, merge_ms=merge_ms, patients_unsupported=[list(u) for u in patients_bad])
+            return _pack_hits(ok, hits, n_hits, stats, sorted(unsupported))
+
+        if job.rank != 0:
+            job.publish("grim_srl_%s_%d" % (job.tag, job.rank), _pack_hits(*mine()))
+        ok, hits, n_hits, stats, unsupported = _unpack_hits(job.from_rank0("grim_srf_" + job.tag, merged))
         stats["unsupported"] = unsupported
         stats["patients_unsupported"] = [tuple(u) for u in stats["patients_unsupported"]]
         result = (ok, hits, n_hits, stats)
-    except BaseException as e:  # the other ranks must not wait for this one: report, reach the barrier, raise
-        if isinstance(e, _PeerFailed):
-            peer_failed = e
-        else:
-            error = e
-            ctl.report_error(tag, "%s: %s\n%s" % (type(e).__name__, e, traceback.format_exc()))
-    finally:
-        if search is not None:
-            search.close()
-    failed = ctl.barrier_and_errors(tag)
-    try:
-        if error is not None:
-            raise error
-        if failed:
-            raise RuntimeError("search_sharded: rank(s) %s failed:\n%s" % ([r for r, _ in failed], failed[0][1]))
-        if peer_failed is not None:
-            raise peer_failed
-    finally:
-        ctl.barrier()  # nobody leaves while another rank still reads the store
-        if ctl.rank == 0 and ctl.world > 1:
-            _discard(ctl, "grim_srf_" + tag)
-            for r in range(1, ctl.world):  # lists a rank published before the job failed: nobody will collect them
-                _discard(ctl, "grim_srl_%s_%d" % (tag, r))
+    job.close()
     return result
-
-
-def _discard(ctl, name):
-    """best effort: the pieces and the head key of a blob published under `name`, if its head key is there"""
-    try:
-        if ctl._has(name):
-            for i in range(int(ctl.store.get(name))):
-                ctl.delete("%s_%d" % (name, i))
-            ctl.delete(name)
-    except Exception:
-        pass
 
 
 def search_file_sharded(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, chunk_lines=None, graph=None, timeout_s=1800,
@@ -908,14 +876,14 @@ def search_file_sharded(conf_file, patients_path, keep_loci, out_path, top_n, mi
     from .blocks import read_lines
     from .imputation.networkx_graph import Graph
     from .run_impute_def import load_config
-    from .search import write_hits_csv
+    from .search import _check, write_hits_csv
 
+    top_n, min_p0 = _check(top_n, min_p0)
     config, _ = load_config(conf_file)
-    if graph is None:
+    if graph is None:  # (the CSV's rows need it too)
         graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
-    ok, hits, n_hits, stats = search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=min_p0, chunk_lines=chunk_lines, graph=graph,
-                                             timeout_s=timeout_s, block_lines=block_lines)
-    ctl = _Control(timeout_s)
+    job = _Job("search_sharded", timeout_s, chunk_lines)
+    ok, hits, n_hits, stats = _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, None, block_lines)
     failure = []
 
     def write():  # on rank 0 (or alone) -> what the other ranks learn: "ok" or the error's text
@@ -927,11 +895,7 @@ def search_file_sharded(conf_file, patients_path, keep_loci, out_path, top_n, mi
             failure.append(e)
             return "%s: %s" % (type(e).__name__, e)
 
-    key = "grim_srcsv_%d" % _next_call()
-    text = ctl.share(key, write)
-    ctl.barrier()  # every rank has read the key
-    if ctl.rank == 0:
-        ctl.delete(key)
+    text = job.agree(write)
     if failure:
         raise failure[0]
     if text != "ok":

@@ -49,6 +49,12 @@ import torch.distributed as dist
 from grim import shard
 dist.init_process_group(backend="gloo")
 os.chdir(WORK)
+published = []  # every store key this rank's jobs set through the one publish routine: pieces and head keys
+def publish(job, name, blob, _publish=shard._Job.publish):
+    keys = _publish(job, name, blob)
+    published.extend(keys)
+    return keys
+shard._Job.publish = publish
 def compute(cfg, lines, offset):
     if FAIL_LINE >= 0 and offset <= FAIL_LINE < offset + len(lines):
         raise ValueError("boom in the chunk of line %d" % FAIL_LINE)
@@ -61,6 +67,9 @@ try:
               open(OUT + ".rank%d" % dist.get_rank(), "w"))
 except Exception as e:
     open(OUT + ".err%d" % dist.get_rank(), "w").write("%.1f %s: %s" % (time.monotonic() - t0, type(e).__name__, e))
+dist.barrier()
+store = dist.distributed_c10d._get_default_store()
+json.dump({"published": published, "left": [k for k in published if store.check([k])]}, open(OUT + ".keys%d" % dist.get_rank(), "w"))
 dist.barrier(); dist.destroy_process_group()
 '''
 
@@ -84,6 +93,12 @@ def _launch(tmp_path, world, chunk, port, tag, fail_line=-1, big=0, timeout_s=12
     subprocess.check_call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                            "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)], env=env, timeout=300)
     return lines, out
+
+
+def _store_keys(out, rank):
+    """{"published": the store keys the rank's job set through its publish routine, "left": those of them still on the store
+    after the job and a barrier}"""
+    return json.load(open(out + ".keys%d" % rank))
 
 
 def _want(lines, chunk, big=0):
@@ -154,6 +169,8 @@ def test_a_failing_chunk_ends_every_rank_well_inside_the_timeout(tmp_path):
     assert sum(e.startswith("ValueError: boom in the chunk of line 42") for _, e in errs) == 1
     assert all(e.startswith("ValueError: boom") or "failed" in e for _, e in errs)
     assert all(float(t) < 60.0 for t, _ in errs)
+    # the tables the surviving ranks published are collected by nobody: none of them outlives the job all the same
+    assert [_store_keys(out, r)["left"] for r in range(3)] == [[], [], []]
 
 
 def test_a_table_above_the_piece_size_survives_the_trip(tmp_path):
@@ -168,3 +185,6 @@ def test_a_table_above_the_piece_size_survives_the_trip(tmp_path):
     assert n_chunks == 2 and len(keys) > big
     assert ranks[0]["keys"] == keys.tolist() and ranks[0]["pops"] == pops.tolist()
     assert ranks[0]["vals"] == [float(v).hex() for v in np.asarray(vals).tolist()]
+    keys = [_store_keys(out, r) for r in range(2)]
+    assert len(keys[0]["published"]) > 2  # rank 0: the final table's pieces and its head key
+    assert [k["left"] for k in keys] == [[], []]  # no blob outlives its job

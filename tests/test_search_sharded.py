@@ -50,6 +50,12 @@ import torch.distributed as dist
 from grim import shard
 dist.init_process_group(backend="gloo")
 os.chdir(WORK)
+published = []  # every store key this rank's jobs set through the one publish routine: pieces and head keys
+def publish(job, name, blob, _publish=shard._Job.publish):
+    keys = _publish(job, name, blob)
+    published.extend(keys)
+    return keys
+shard._Job.publish = publish
 def compute(cfg, plines, lines, first):
     if FAIL_LINE >= 0 and first <= FAIL_LINE < first + len(lines):
         raise ValueError("boom in the chunk of line %d" % FAIL_LINE)
@@ -63,6 +69,9 @@ for chunk in CHUNKS:
         json.dump({"ok": ok.tolist(), "n_hits": n_hits.tolist(), "stats": stats}, open(OUT + ".c%d.rank%d" % (chunk, dist.get_rank()), "w"))
     except Exception as e:
         open(OUT + ".err%d" % dist.get_rank(), "w").write("%.1f %s: %s" % (time.monotonic() - t0, type(e).__name__, e))
+dist.barrier()
+store = dist.distributed_c10d._get_default_store()
+json.dump({"published": published, "left": [k for k in published if store.check([k])]}, open(OUT + ".keys%d" % dist.get_rank(), "w"))
 dist.barrier(); dist.destroy_process_group()
 '''
 
@@ -89,6 +98,12 @@ def _launch(tmp_path, world, chunks, port, tag, n_patients=5, top_n=20, min_p0=0
     subprocess.check_call([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                            "--master-addr", "127.0.0.1", "--master-port", str(port), str(script)], env=env, timeout=300)
     return lines, out
+
+
+def _store_keys(out, rank):
+    """{"published": the store keys the rank's jobs set through their publish routine, "left": those of them still on the
+    store after the jobs and a barrier}"""
+    return json.load(open(out + ".keys%d" % rank))
 
 
 def _want(lines, chunk, n_patients, top_n, min_p0):
@@ -163,6 +178,10 @@ def test_a_failing_chunk_ends_every_rank_well_inside_the_timeout(tmp_path):
     assert sum(e.startswith("ValueError: boom in the chunk of line 42") for _, e in errs) == 1
     assert all(e.startswith("ValueError: boom") or "failed" in e for _, e in errs)
     assert all(float(t) < 60.0 for t, _ in errs)
+    # a surviving rank other than 0 has published its lists, and nobody collects them: none outlives the job all the same
+    keys = [_store_keys(out, r) for r in range(3)]
+    assert sum(len(k["published"]) for k in keys) > 0
+    assert [k["left"] for k in keys] == [[], [], []]
 
 
 def test_hit_lists_above_the_piece_size_survive_the_trip(tmp_path):
@@ -177,3 +196,6 @@ def test_hit_lists_above_the_piece_size_survive_the_trip(tmp_path):
     assert hits[0] == hits[1] and rest[0] == rest[1]
     _check(hits[0], rest[0], want, n_patients)
     assert want[3] == 2 and want[1].tolist() == [N_LINES] * n_patients
+    keys = [_store_keys(out, r) for r in range(2)]
+    assert all(len(k["published"]) > 2 for k in keys)  # rank 1's lists and rank 0's final ones: pieces and a head key each
+    assert [k["left"] for k in keys] == [[], []]  # no blob outlives its job
