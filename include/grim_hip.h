@@ -733,6 +733,58 @@ double grim_search_kernel_ms(const grim_search *s);
 double grim_search_select_ms(const grim_search *s);
 void grim_search_free(grim_search *s);
 
+/* ======================= allele groups: the consumers above at a chosen resolution (csrc/grim_groups.h) =================
+ * The marginal tables, the match and the search compare alleles by dictionary id: at the resolution the graph was built at.
+ * A group map puts a mapping pass in front of their kernels, which stay exactly as they are.
+ * Group map: for every locus slot s a table T_s[0 .. n_alleles[s]] of uint16_t and a count n_groups[s].  T_s[0] == 0 (untyped
+ *   stays untyped); 1 <= T_s[f] <= n_groups[s] for 1 <= f <= n_alleles[s]; every group id in 1..n_groups[s] occurs; hence
+ *   n_groups[s] <= n_alleles[s] <= 4095.  A slot with T_s[f] = f is an identity slot; watch_mask = the slots that are not.
+ * Mapped row: (a, b, prob, popa, popb) -> (map(a), map(b), prob, popa, popb); the 12-bit field f of slot s becomes
+ *     0                                  if f == 0
+ *     T_s[f]                             if 1 <= f <= n_alleles[s]
+ *     n_groups[s] + (f - n_alleles[s])   if f > n_alleles[s]: an allele private to the subject stays private, distinct from
+ *                                        every group and from the subject's other private alleles, and keeps its index;
+ *   the result is <= f, so a field never overflows.  Key bits at GRIM_KEY_GRAPH_ORDER and above are copied.  No
+ *   floating-point operation takes place.
+ * Consumers on mapped rows: with a map attached a consumer runs its contract above on the mapped rows, n_groups in the place
+ *   of n_alleles, every rule word for word: the marginal's leaders, left-to-right sums and ranks; the matcher's flags, eq,
+ *   M(i,j) and fold order (GRIM_MATCH_PRIVATE: a field above n_groups[s] in a slot of K); the search's order.  With every slot
+ *   an identity slot every output byte equals the call without a map.  Without a map a consumer executes exactly the launches
+ *   it did before.
+ * Private alleles are the host's: the device cannot know which group an unseen allele's text belongs to.  Match and search
+ *   leave such pairs out as before (the caller folds them on group names).  The marginal flags a subject
+ *   GRIM_GROUPS_PRIVATE when its rows can be read (status GRIM_ST_OK, rows inside the rows given) and some GRIM_T_UMUG row
+ *   holds a private field in a slot of keep_mask & watch_mask; the caller folds those subjects on text.  Private alleles in
+ *   identity slots need no special case.
+ * Environment, read when a map is created: GRIM_GROUPS_LDS=0 makes the map kernel read the tables where they lie instead of
+ *   staging them in LDS in every workgroup, the default (for measurements). */
+#define GRIM_GROUPS_PRIVATE 1
+typedef struct grim_groups grim_groups;
+/* table: the slots' tables back to back, each of length n_alleles[s] + 1.  Every rule above is checked on the host before any
+ * upload; a refusal returns NULL with a grim_last_error text that names the slot and the entry, and launches nothing */
+grim_groups *grim_groups_create(grim_ctx *ctx, const uint16_t *table, const uint32_t n_alleles[GRIM_MAXL],
+                                const uint32_t n_groups[GRIM_MAXL]);
+void grim_groups_free(grim_groups *g);
+uint32_t grim_groups_watch_mask(const grim_groups *g);
+/* rows[n_rows] (host) uploaded, mapped, downloaded into out[n_rows]; synchronous.  n_rows == 0 answers 0 with no launch; -3
+ * for a null array with rows or n_rows above 2^31 - 1 */
+int grim_groups_map_records(grim_groups *g, const grim_row *rows, uint64_t n_rows, grim_row *out);
+/* device time of the map kernel of the last grim_groups_map_records, between its own start/stop events (64 bytes move per
+ * row) */
+double grim_groups_kernel_ms(const grim_groups *g);
+/* Attach a map to a consumer (g == NULL detaches).  The consumer copies the tables device to device into a buffer of its own:
+ * g may be freed right after.  The last results are cleared first.  -3 with a text: g belongs to another context; for match
+ * and search, g's n_alleles differ from the ones given at create.  On a matcher, setting or detaching drops the patients, as
+ * grim_match_set_patients does first; on a search it also empties the hit lists and the summed statistics: rows prepared, or
+ * hits computed, at one resolution never meet another.  From then on both doors of the consumer (and
+ * grim_match_set_patients) map the rows into a buffer of the consumer's between its two event records -- kernel_ms includes
+ * the pass -- and hand that buffer to the kernels in place of the rows.  grim_search_merge_hits is untouched. */
+int grim_marginal_set_groups(grim_marginal *m, const grim_groups *g);
+int grim_match_set_groups(grim_match *m, const grim_groups *g);
+int grim_search_set_groups(grim_search *s, const grim_groups *g);
+/* out[grim_marginal_subjects]: GRIM_GROUPS_PRIVATE or 0 per subject of the last reduce; all zero when it ran without a map */
+int grim_marginal_flags(grim_marginal *m, uint8_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@
 #include "grim_marginal.h"
 #include "grim_match.h"
 #include "grim_search.h"
+#include "grim_groups.h"
 #include "grim_engine_internal.h"
 #include "grim_host_internal.h"
 #include "grim_sdma.h"
@@ -2495,6 +2496,187 @@ extern "C" double grim_graph_refresh_ms(const grim_graph *g) { return g ? g->ref
 extern "C" int grim_graph_refreshable(const grim_graph *g) { return g && g->refreshable ? 1 : 0; }
 
 // =================================================================================================
+// Allele groups (grim_groups.h): the rows mapped to a chosen resolution in front of the consumers below
+// =================================================================================================
+struct grim_groups {
+  grim_ctx *ctx;
+  GpMap M;  // M.tab = d_tab
+  uint32_t watch_mask;
+  bool staged;
+  DevBuf<uint16_t> d_tab;
+  DevBuf<grim_row> d_in, d_out;  // of grim_groups_map_records
+  Events<2> ev;
+  double last_ms;
+};
+
+// what a consumer keeps of a group map: its own copy of the tables (its lifetime does not depend on the grim_groups) and the
+// buffer the mapped rows go to
+struct GpAttach {
+  bool on = false, staged = false;
+  GpMap M = {};
+  uint32_t watch_mask = 0;
+  DevBuf<uint16_t> tab;
+  DevBuf<grim_row> mapped;
+  void detach() { on = false; }
+  // the tables of g, device to device; ends in a stream synchronise
+  int attach(grim_ctx *c, const char *who, const grim_groups *g) {
+    on = false;
+    if (!tab.reserve((uint64_t)g->M.total + 1)) {  // never an empty allocation
+      set_err(c, std::string(who) + ": device allocation failed");
+      return -1;
+    }
+    HIPCHK(hipMemcpyAsync(tab, g->d_tab, sizeof(uint16_t) * (uint64_t)g->M.total, hipMemcpyDeviceToDevice, c->stream), c, -1);
+    HIPCHK(hipStreamSynchronize(c->stream), c, -1);
+    M = g->M;
+    M.tab = tab;
+    watch_mask = g->watch_mask;
+    staged = g->staged;
+    on = true;
+    return 0;
+  }
+  EmLimits limits() const {
+    EmLimits L;
+    for (int q = 0; q < GRIM_MAXL; ++q) L.n_alleles[q] = M.n_groups[q];
+    return L;
+  }
+};
+
+// rows[0 .. rows_used) through the map into out (device arrays of at least rows_used rows, 16-byte aligned); enqueues only
+static bool gp_launch(hipStream_t st, const GpMap &M, bool staged, const grim_row *rows, uint32_t rows_used, grim_row *out) {
+  if (rows_used == 0) return true;
+  if (((uintptr_t)rows | (uintptr_t)out) & 15u) return false;
+  const uint32_t need = (rows_used + GP_THREADS - 1) / GP_THREADS, blocks = need < GP_MAX_BLOCKS ? need : GP_MAX_BLOCKS;
+  if (staged)
+    hipLaunchKernelGGL(gp_map_kernel<true>, dim3(blocks), dim3(GP_THREADS), 0, st, rows, rows_used, M, out);
+  else
+    hipLaunchKernelGGL(gp_map_kernel<false>, dim3(blocks), dim3(GP_THREADS), 0, st, rows, rows_used, M, out);
+  return true;
+}
+
+// a consumer's rows through its map into its own buffer; rows then names the mapped rows.  Reserves before it launches.
+static int gp_map_rows(grim_ctx *c, const char *who, GpAttach &A, const grim_row *&rows, uint32_t rows_used) {
+  if (!A.mapped.reserve((uint64_t)rows_used + 1, rows_used / 4)) {  // never an empty allocation
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
+  }
+  if (!gp_launch(c->stream, A.M, A.staged, rows, rows_used, A.mapped)) {
+    set_err(c, std::string(who) + ": the rows are not 16-byte aligned (internal)");
+    return -1;
+  }
+  HIPCHK(hipGetLastError(), c, -1);
+  rows = A.mapped;
+  return 0;
+}
+
+extern "C" grim_groups *grim_groups_create(grim_ctx *c, const uint16_t *table, const uint32_t n_alleles[GRIM_MAXL],
+                                           const uint32_t n_groups[GRIM_MAXL]) {
+  if (!c || !table || !n_alleles || !n_groups) {
+    set_err(c, "grim_groups_create: bad arguments");
+    return nullptr;
+  }
+  const std::string who = "grim_groups_create: slot ";
+  GpMap M = {};
+  uint32_t watch = 0;
+  for (int q = 0; q < GRIM_MAXL; ++q) {  // the sizes first: nothing of a table is read before they are known to be sane
+    if (n_alleles[q] > 4095u) {
+      set_err(c, who + std::to_string(q) + ": n_alleles " + std::to_string(n_alleles[q]) + " is above 4095");
+      return nullptr;
+    }
+    if (n_groups[q] > n_alleles[q]) {
+      set_err(c, who + std::to_string(q) + ": n_groups " + std::to_string(n_groups[q]) + " is above n_alleles " + std::to_string(n_alleles[q]));
+      return nullptr;
+    }
+    M.off[q] = M.total;
+    M.n_alleles[q] = n_alleles[q];
+    M.n_groups[q] = n_groups[q];
+    M.total += n_alleles[q] + 1u;
+  }
+  for (int q = 0; q < GRIM_MAXL; ++q) {
+    const uint16_t *T = table + M.off[q];
+    if (T[0] != 0) {
+      set_err(c, who + std::to_string(q) + ", entry 0: " + std::to_string(T[0]) + ", not 0 (untyped stays untyped)");
+      return nullptr;
+    }
+    std::vector<uint8_t> used(n_groups[q] + 1u, 0);
+    for (uint32_t f = 1; f <= n_alleles[q]; ++f) {
+      if (T[f] == 0 || T[f] > n_groups[q]) {
+        set_err(c, who + std::to_string(q) + ", entry " + std::to_string(f) + ": group " + std::to_string(T[f]) + " is not in 1.." +
+                       std::to_string(n_groups[q]));
+        return nullptr;
+      }
+      used[T[f]] = 1;
+      if (T[f] != f) watch |= 1u << q;
+    }
+    for (uint32_t gid = 1; gid <= n_groups[q]; ++gid)
+      if (!used[gid]) {
+        set_err(c, who + std::to_string(q) + ": group " + std::to_string(gid) + " is used by no entry");
+        return nullptr;
+      }
+  }
+  bool staged = true;  // measured (profiles/groups_notes.md): every workgroup stages the tables in LDS
+  if (const char *e = getenv("GRIM_GROUPS_LDS")) staged = e[0] != '0';  // for the bench: 0 reads the tables where they lie
+  use_device(c->device);
+  grim_groups *g = new grim_groups();
+  g->ctx = c;
+  g->M = M;
+  g->watch_mask = watch;
+  g->staged = staged;
+  if (!g->d_tab.reserve((uint64_t)M.total + 1) || !g->ev.create()) {  // never an empty allocation
+    (void)hipGetLastError();
+    set_err(c, "grim_groups_create: device allocation failed");
+    grim_groups_free(g);
+    return nullptr;
+  }
+  g->M.tab = g->d_tab;
+  if (hipMemcpyAsync(g->d_tab, table, sizeof(uint16_t) * (uint64_t)M.total, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipGetLastError();
+    set_err(c, "grim_groups_create: the upload of the tables failed");
+    grim_groups_free(g);
+    return nullptr;
+  }
+  return g;
+}
+
+extern "C" void grim_groups_free(grim_groups *g) {
+  if (!g) return;
+  use_device(g->ctx->device);
+  hipStreamSynchronize(g->ctx->stream);
+  delete g;
+}
+
+extern "C" uint32_t grim_groups_watch_mask(const grim_groups *g) { return g ? g->watch_mask : 0; }
+extern "C" double grim_groups_kernel_ms(const grim_groups *g) { return g ? g->last_ms : 0.0; }
+
+extern "C" int grim_groups_map_records(grim_groups *g, const grim_row *rows, uint64_t n_rows, grim_row *out) {
+  if (!g) return -1;
+  grim_ctx *c = g->ctx;
+  g->last_ms = 0.0;
+  if ((n_rows && (!rows || !out)) || n_rows > 0x7FFFFFFFull) {
+    set_err(c, "grim_groups_map_records: bad arguments");
+    return -3;
+  }
+  if (n_rows == 0) return 0;
+  use_device(c->device);
+  hipStream_t st = c->stream;
+  if (!reserve_all(n_rows + 1, 0, g->d_in, g->d_out)) {  // never an empty allocation
+    set_err(c, "grim_groups_map_records: device allocation failed");
+    return -1;
+  }
+  HIPCHK(hipMemcpyAsync(g->d_in, rows, sizeof(grim_row) * n_rows, hipMemcpyHostToDevice, st), c, -1);
+  HIPCHK(hipEventRecord(g->ev[0], st), c, -1);
+  if (!gp_launch(st, g->M, g->staged, g->d_in, (uint32_t)n_rows, g->d_out)) return -1;
+  HIPCHK(hipGetLastError(), c, -1);
+  HIPCHK(hipEventRecord(g->ev[1], st), c, -1);
+  HIPCHK(hipMemcpyAsync(out, g->d_out, sizeof(grim_row) * n_rows, hipMemcpyDeviceToHost, st), c, -1);
+  HIPCHK(hipStreamSynchronize(st), c, -1);
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]), c, -1);
+  g->last_ms = ms;
+  return 0;
+}
+
+// =================================================================================================
 // Marginal genotype tables (grim_marginal.h): the UMUG rows of a finished batch reduced to a subset of the loci
 // =================================================================================================
 struct grim_marginal {
@@ -2509,6 +2691,9 @@ struct grim_marginal {
   DevBuf<grim_row> d_orows;
   DevBuf<grim_subject_result> d_ores;
   RecordsUpload in;
+  GpAttach gp;  // the group map attached (grim_marginal_set_groups) and the subjects' GRIM_GROUPS_PRIVATE flags
+  DevBuf<uint8_t> d_flags;
+  bool have_flags;  // the last reduce ran with a map attached
   // the last reduce
   uint32_t n_subj, n_rows;
   uint64_t stat[5];
@@ -2544,6 +2729,7 @@ extern "C" void grim_marginal_free(grim_marginal *m) {
 
 static void mg_clear(grim_marginal *m) {
   m->n_subj = m->n_rows = 0;
+  m->have_flags = false;
   for (uint64_t &x : m->stat) x = 0;
   m->last_ms = 0.0;
 }
@@ -2558,10 +2744,22 @@ static int mg_run(grim_marginal *m, const char *who, const grim_subject_result *
     set_err(c, std::string(who) + ": device allocation failed");
     return -1;
   }
+  const bool grouped = m->gp.on;
+  if (grouped && (!m->d_flags.reserve((uint64_t)n + 1) || !m->gp.mapped.reserve((uint64_t)rows_used + 1, rows_used / 4))) {
+    set_err(c, std::string(who) + ": device allocation failed");
+    return -1;
+  }
   const MgScratch G = {m->g_lo, m->g_hi, m->g_prob, m->g_sum, m->g_lead};
   HIPCHK(hipMemsetAsync(m->d_stat, 0, 8 * MG_S_COUNT * MG_S_SLICES, st), c, -1);
   if (rows_used) HIPCHK(hipMemsetAsync(m->d_orows, 0, sizeof(grim_row) * (uint64_t)rows_used, st), c, -1);  // what a region does not use reads as zeros
   HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
+  if (grouped) {  // the flags from the rows as they came, then the rows through the map: the kernels below see the mapped rows
+    EmLimits L;
+    for (int q = 0; q < GRIM_MAXL; ++q) L.n_alleles[q] = m->gp.M.n_alleles[q];
+    hipLaunchKernelGGL(gp_flag_kernel, dim3((n + 3) / 4), dim3(256), 0, st, res, rows, n, rows_used, L, m->keep_mask & m->gp.watch_mask,
+                       m->d_flags);
+    if (gp_map_rows(c, who, m->gp, rows, rows_used) != 0) return -1;
+  }
   hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, m->d_first);
   hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, m->d_first, n);
   hipLaunchKernelGGL(mg_reduce_kernel, dim3(n), dim3(64), 0, st, res, rows, n, rows_used, m->d_first, rows_used, m->keep_mask, m->max_rows,
@@ -2581,6 +2779,7 @@ static int mg_run(grim_marginal *m, const char *who, const grim_subject_result *
   m->last_ms = ms;
   m->n_subj = n;
   m->n_rows = total;
+  m->have_flags = grouped;
   for (int k = 0; k < 5; ++k) m->stat[k] = h[k];
   return 0;
 }
@@ -2619,6 +2818,33 @@ extern "C" int grim_marginal_results(grim_marginal *m, grim_subject_result *res,
   return 0;
 }
 
+extern "C" int grim_marginal_set_groups(grim_marginal *m, const grim_groups *g) {
+  if (!m) return -1;
+  grim_ctx *c = m->ctx;
+  mg_clear(m);
+  m->gp.detach();
+  if (!g) return 0;
+  if (g->ctx != c) {
+    set_err(c, "grim_marginal_set_groups: the groups belong to another context");
+    return -3;
+  }
+  use_device(c->device);
+  return m->gp.attach(c, "grim_marginal_set_groups", g);
+}
+
+extern "C" int grim_marginal_flags(grim_marginal *m, uint8_t *out) {
+  if (!m || (m->n_subj && !out)) return -1;
+  grim_ctx *c = m->ctx;
+  if (!m->n_subj) return 0;
+  if (!m->have_flags) {
+    memset(out, 0, m->n_subj);
+    return 0;
+  }
+  use_device(c->device);
+  HIPCHK(hipMemcpy(out, m->d_flags, m->n_subj, hipMemcpyDeviceToHost), c, -1);
+  return 0;
+}
+
 extern "C" int grim_marginal_stats(const grim_marginal *m, uint64_t out[5]) {
   if (!m || !out) return -1;
   for (int k = 0; k < 5; ++k) out[k] = m->stat[k];
@@ -2646,6 +2872,7 @@ struct grim_match {
   // the uploaded records of grim_match_set_patients and of grim_match_run_records (one pair of buffers: mt_prepare copies
   // what a side needs out of them); the result records
   RecordsUpload in;
+  GpAttach gp;  // the group map attached (grim_match_set_groups): both sides' rows go through it before mt_prepare_kernel
   DevBuf<double> d_out;
   bool have_patients;
   uint64_t pstat[MT_S_COUNT];  // what preparing the patients counted
@@ -2705,10 +2932,11 @@ static int mt_prepare(grim_match *m, const char *who, MtBuf &S, uint32_t side, c
     set_err(c, std::string(who) + ": device allocation failed");
     return -1;
   }
+  if (m->gp.on && gp_map_rows(c, who, m->gp, rows, rows_used) != 0) return -1;  // n_groups then stands where n_alleles stood
   hipLaunchKernelGGL(mg_count_kernel, dim3((n + 255) / 256), dim3(256), 0, st, res, n, rows_used, S.first);
   hipLaunchKernelGGL(em_scan_kernel, dim3(1), dim3(1024), 0, st, S.first, n);
   hipLaunchKernelGGL(mt_prepare_kernel, dim3((n + 3) / 4), dim3(256), 0, st, res, rows, n, rows_used, S.first, rows_used, m->keep_mask,
-                     m->lim, side, S.a, S.b, S.w, S.flags, m->d_stat);
+                     m->gp.on ? m->gp.limits() : m->lim, side, S.a, S.b, S.w, S.flags, m->d_stat);
   HIPCHK(hipGetLastError(), c, -1);
   return 0;
 }
@@ -2740,6 +2968,26 @@ extern "C" int grim_match_set_patients(grim_match *m, const grim_subject_result 
   m->P.n = n;
   m->have_patients = true;
   return 0;
+}
+
+extern "C" int grim_match_set_groups(grim_match *m, const grim_groups *g) {
+  if (!m) return -1;
+  grim_ctx *c = m->ctx;
+  mt_clear(m);
+  mt_drop_patients(m);  // rows prepared at one resolution never meet donors at another
+  m->gp.detach();
+  if (!g) return 0;
+  if (g->ctx != c) {
+    set_err(c, "grim_match_set_groups: the groups belong to another context");
+    return -3;
+  }
+  for (int q = 0; q < GRIM_MAXL; ++q)
+    if (g->M.n_alleles[q] != m->lim.n_alleles[q]) {
+      set_err(c, "grim_match_set_groups: slot " + std::to_string(q) + ": the groups' n_alleles differ from the ones given at create");
+      return -3;
+    }
+  use_device(c->device);
+  return m->gp.attach(c, "grim_match_set_groups", g);
 }
 
 // donors (device arrays) against the patients set
@@ -2916,6 +3164,12 @@ extern "C" int grim_search_set_patients(grim_search *s, const grim_subject_resul
   if (!s) return -1;
   sr_empty(s);
   return grim_match_set_patients(s->m, res, n, rows, n_rows);
+}
+
+extern "C" int grim_search_set_groups(grim_search *s, const grim_groups *g) {
+  if (!s) return -1;
+  sr_empty(s);  // a hit list computed at one resolution never meets another
+  return grim_match_set_groups(s->m, g);
 }
 
 extern "C" int grim_search_reset(grim_search *s) {

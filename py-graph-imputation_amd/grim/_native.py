@@ -498,6 +498,81 @@ class EmAccumulator(_Handle):
         return float(_em_lib().grim_em_merge_ms(self.h))
 
 
+# ---- allele groups (grim_groups_*): the rows of the three consumers below mapped to a chosen resolution first ----
+EXPORTS += [
+    "grim_groups_create", "grim_groups_free", "grim_groups_watch_mask", "grim_groups_map_records", "grim_groups_kernel_ms",
+    "grim_marginal_set_groups", "grim_match_set_groups", "grim_search_set_groups", "grim_marginal_flags",
+]
+
+GROUPS_PRIVATE = 1
+
+_groups_ready = False
+
+
+def _groups_lib():
+    global _groups_ready
+    L = lib()
+    if not _groups_ready:
+        L.grim_groups_create.restype = C.c_void_p
+        L.grim_groups_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.grim_groups_free.argtypes = [C.c_void_p]
+        L.grim_groups_watch_mask.restype = C.c_uint32
+        L.grim_groups_watch_mask.argtypes = [C.c_void_p]
+        L.grim_groups_map_records.restype = C.c_int
+        L.grim_groups_map_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.grim_groups_kernel_ms.restype = C.c_double
+        L.grim_groups_kernel_ms.argtypes = [C.c_void_p]
+        for name in ("grim_marginal_set_groups", "grim_match_set_groups", "grim_search_set_groups", "grim_marginal_flags"):
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        _groups_ready = True
+    return L
+
+
+class Groups(_Handle):
+    """grim_groups: a group map on the device (include/grim_hip.h, the grim_groups_* block).  `table`: the slots' uint16 tables
+    back to back, each of length n_alleles[s] + 1 (AlleleGroups.flat()); a map the library refuses raises NativeError with its
+    text.  A consumer copies the tables when the map is attached, so the map may be closed right after."""
+
+    _free = "grim_groups_free"
+
+    def __init__(self, ctx, table, n_alleles, n_groups):
+        L = _groups_lib()
+        self.ctx = ctx
+        na = [int(x) for x in n_alleles] + [0] * (MAXL - len(n_alleles))
+        ng = [int(x) for x in n_groups] + [0] * (MAXL - len(n_groups))
+        table = np.ascontiguousarray(table, dtype=np.uint16)
+        need = sum(min(x, 4095) + 1 for x in na)  # the library reads no table before it has checked the sizes
+        if table.ndim != 1 or len(table) < need:
+            raise ValueError("the table holds %d entries, the slots need %d" % (table.size, need))
+        self.h = L.grim_groups_create(ctx.h, _ptr(table), (C.c_uint32 * MAXL)(*na), (C.c_uint32 * MAXL)(*ng))
+        if not self.h:
+            raise NativeError("grim_groups_create failed: " + ctx.error())
+
+    @classmethod
+    def of(cls, ctx, groups):
+        """an AlleleGroups (grim.groups) on the device"""
+        return cls(ctx, groups.flat(), groups.n_alleles, groups.n_groups)
+
+    def watch_mask(self):
+        return int(_groups_lib().grim_groups_watch_mask(self.h))
+
+    def map_records(self, rows):
+        """ROW_DT rows through gp_map_kernel -> the mapped rows"""
+        rows = np.ascontiguousarray(rows, dtype=ROW_DT)
+        out = np.zeros(max(len(rows), 1), dtype=ROW_DT)
+        self._check(_groups_lib().grim_groups_map_records(self.h, _ptr(rows) if rows.size else None, len(rows), _ptr(out)),
+                    "grim_groups_map_records")
+        return out[:len(rows)]
+
+    def kernel_ms(self):
+        return float(_groups_lib().grim_groups_kernel_ms(self.h))
+
+
+def _set_groups(obj, name, groups):
+    obj._check(getattr(_groups_lib(), name)(obj.h, groups.h if groups is not None else None), name)
+
+
 # ---- marginal genotype tables (grim_marginal_*): the UMUG rows of finished batches reduced to a subset of the loci ----
 EXPORTS += [
     "grim_marginal_create", "grim_marginal_reduce", "grim_marginal_reduce_records", "grim_marginal_subjects",
@@ -557,6 +632,16 @@ class MarginalReducer(_Handle):
         """host records (RESULT_DT[n], ROW_DT[m]) through the same kernels"""
         res, rows, args = _records(res, rows)
         self._check(_marginal_lib().grim_marginal_reduce_records(self.h, *args), "grim_marginal_reduce_records")
+
+    def set_groups(self, groups):
+        """a Groups map for every reduce that follows (None detaches); the last results are cleared"""
+        _set_groups(self, "grim_marginal_set_groups", groups)
+
+    def flags(self):
+        """-> u8[subjects] of the last reduce: GROUPS_PRIVATE where the host has to fold the subject on text; zeros without a map"""
+        out = np.zeros(max(self.subjects(), 1), dtype=np.uint8)
+        self._check(_groups_lib().grim_marginal_flags(self.h, _ptr(out)), "grim_marginal_flags", code=False)
+        return out[:self.subjects()]
 
     def subjects(self):
         return int(_marginal_lib().grim_marginal_subjects(self.h))
@@ -639,6 +724,10 @@ class Matcher(_Handle):
         self.h = L.grim_match_create(ctx.h, int(keep_mask), arr)
         if not self.h:
             raise NativeError("grim_match_create failed: " + ctx.error())
+
+    def set_groups(self, groups):
+        """a Groups map for everything that follows (None detaches); drops the patients and the last results"""
+        _set_groups(self, "grim_match_set_groups", groups)
 
     def set_patients(self, res, rows):
         """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows"""
@@ -755,6 +844,10 @@ class Searcher(_Handle):
         if ids.shape != (n,):
             raise ValueError("%d donors but ids of shape %r" % (n, ids.shape))
         return ids
+
+    def set_groups(self, groups):
+        """a Groups map for everything that follows (None detaches); drops the patients, empties the hit lists and the sums"""
+        _set_groups(self, "grim_search_set_groups", groups)
 
     def set_patients(self, res, rows):
         """host records (RESULT_DT[n], ROW_DT[m]) as the patients of every run that follows; empties the hit lists"""

@@ -29,6 +29,7 @@ import numpy as np
 
 from . import _native as nat
 from .blocks import Blocks, note_unsupported, read_lines
+from .groups import as_groups, regroup_umug_text
 from .marginal import keep_mask as _keep_mask
 
 
@@ -138,12 +139,18 @@ def _side(res, rows, slots, n_alleles, folder):
     return flags, subs
 
 
-def match_records(pres, prows, dres, drows, keep_mask, n_alleles):
+def match_records(pres, prows, dres, drows, keep_mask, n_alleles, groups=None):
     """The fold on record arrays (nat.RESULT_DT / nat.ROW_DT of the patients and of the donors) as grim_match_run_records
     defines it (include/grim_hip.h) -> (records nat.MATCH_DT[P][D], patient flags, donor flags, stats), laid out as the device
-    lays them out: a pair that is not computed is a record of zeros; without donors every statistic is 0."""
+    lays them out: a pair that is not computed is a record of zeros; without donors every statistic is 0.  `groups`: an
+    AlleleGroups (grim.groups) whose n_alleles are the ones given: both sides' rows are mapped first and n_groups stands in
+    the place of n_alleles, as on the device with the map attached."""
     slots = _slots_of(keep_mask)
     n_alleles = [int(x) for x in n_alleles] + [0] * (nat.MAXL - len(n_alleles))
+    if groups is not None:
+        if list(groups.n_alleles) != n_alleles:
+            raise ValueError("the groups' n_alleles differ from the ones given")
+        prows, drows, n_alleles = groups.map_records(prows), groups.map_records(drows), list(groups.n_groups)
     folder = _Folder(len(slots))
     pflags, psubs = _side(pres, prows, slots, n_alleles, folder)
     dflags, dsubs = _side(dres, drows, slots, n_alleles, folder)
@@ -199,12 +206,15 @@ def _text_subjects(text, keep):
     return subs
 
 
-def match_umug_text(patient_text, donor_text, keep_loci, loci=None):
+def match_umug_text(patient_text, donor_text, keep_loci, loci=None, groups=None):
     """The fold on `.umug` text in `id,genotype,p,rank` form -> (patient ids, donor ids, records[P][D]); a record is
     (mm[0..2|K|], {locus name: probability of no mismatch}).  A subject is the run of rows from one rank 0 to the next; a
     `^`-part of a genotype belongs to the locus named before its first `*`, its two alleles are the `+`-separated texts; a
     kept locus a row lacks is untyped; two alleles are equal when their texts are.  `loci`: the names that may be kept (an
-    unknown one raises)."""
+    unknown one raises); `groups`: a group specification (grim.groups.GroupSpec or what it takes): both texts go through
+    `regroup_umug_text` first."""
+    if groups is not None:
+        patient_text, donor_text = regroup_umug_text(patient_text, groups), regroup_umug_text(donor_text, groups)
     keep = [keep_loci] if isinstance(keep_loci, str) else list(dict.fromkeys(keep_loci))
     if not keep:
         raise ValueError("keep_loci is empty")
@@ -247,9 +257,10 @@ class _Pairing:
     Matcher or a Searcher), the donors cut into blocks, the check of a block's flags, and the host fold of the pairs the
     device leaves out.  The callers run each donor block themselves and do what they like with the pairs."""
 
-    def __init__(self, imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em):
+    def __init__(self, imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups=None):
         self.imputation = imputation
         self.g = g = imputation.netGraph
+        self.groups = as_groups(g, groups)  # None: alleles compare as the dictionary has them
         self.mask = _keep_mask(g.locus_slot, keep_loci)
         self.slots = _slots_of(self.mask)
         self.dlines = [] if donor_lines_or_path is None else read_lines(donor_lines_or_path)  # None: given per donor_blocks call
@@ -270,7 +281,13 @@ class _Pairing:
     def set_patients(self, dev, patient_flags, stats):
         """the patients as one block onto `dev`; `patient_flags`: () -> their flags on the device.  Their batch is closed as
         soon as they are set: the records are on the host, the patients prepared on the device; the tokenised lines stay for
-        the text route."""
+        the text route.  The group map, when there is one, is attached first (that drops whatever patients `dev` held)."""
+        if self.groups is not None:
+            dev_groups = nat.Groups.of(self.ctx, self.groups)
+            try:
+                dev.set_groups(dev_groups)  # `dev` keeps its own copy of the tables
+            finally:
+                dev_groups.close()
         self.pblock = self.blocks.block(self.plines)
         if self.pblock.batch is not None:
             dev.set_patients(*self.pblock.records())
@@ -325,7 +342,8 @@ class _Pairing:
             if f == 0:
                 return None
             if (s, f) not in names:  # an id above the dictionary's is the line's own
-                names[(s, f)] = block.parsed.allele(line, s, f - 1) if f > self.n_alleles[s] else self.g.key_alleles(f << (nat.ABITS * s))[s]
+                name = block.parsed.allele(line, s, f - 1) if f > self.n_alleles[s] else self.g.key_alleles(f << (nat.ABITS * s))[s]
+                names[(s, f)] = name if self.groups is None else self.groups.spec.name(self.g.slot_locus[s], name)
             return names[(s, f)]
 
         ps = [float(rows[off + k]["prob"]) for k in range(n)]
@@ -343,7 +361,8 @@ class _Pairing:
             self.pblock.close()
 
 
-def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines=65536, planb=None, em=False):
+def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines=65536, planb=None, em=False,
+                        groups=None):
     """Match probabilities of every patient against every donor on the device.  `patient_lines`: input lines;
     `donor_lines_or_path`: input lines (a list) or the path of an input file; `config`: the configuration dict of
     `load_config`; `keep_loci`: locus names of its loci_map.  The patients are imputed as one device batch, their records
@@ -353,8 +372,10 @@ def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, 
     here on allele text.  -> (patient_ok, donor_ok, records, stats): records is nat.MATCH_DT[len(patient_lines)][len(donor
     lines)], zero for lines without genotype rows; *_ok say which lines have them; stats adds `blocks`, `kernel_ms` and
     `host_pairs` (pairs folded on text).  The cuts do not show in any byte.  Subjects the device cannot answer follow
-    `imputation.on_unsupported` as in `impute_lines_block`."""
-    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em)
+    `imputation.on_unsupported` as in `impute_lines_block`.  `groups`: an AlleleGroups of the imputation's graph or a group
+    specification (grim.groups): alleles are equal when their groups are -- on the device by group id, in the pairs folded
+    here by group name -- and the result equals `match_umug_text` on the regrouped text."""
+    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups)
     matcher = nat.Matcher(pairing.ctx, pairing.mask, pairing.n_alleles)
     stats = dict.fromkeys(nat.MATCH_STATS, 0)
     stats.update(blocks=0, kernel_ms=0.0, host_pairs=0)
@@ -391,11 +412,11 @@ def line_id(line):
     return line.split("," if "," in line else "%", 1)[0]
 
 
-def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0=0.0, block_lines=65536):
+def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0=0.0, block_lines=65536, groups=None):
     """The configuration's input file as donors against the input file `patients_path`, on `graph` (built from the
     configuration's graph CSVs when None) -> a CSV at `out_path`: a header `patient_id,donor_id,mm0,...,mm{2|K|},<kept locus
     names>`, then one line per computed pair with mm0 >= min_p0, patient-major, floats written with repr.  Paths are taken
-    as the configuration gives them.  -> stats"""
+    as the configuration gives them.  `groups`: as `match_probabilities`.  -> stats"""
     from .grim import graph_instance
     from .imputation.impute import Imputation
     from .run_impute_def import load_config
@@ -405,7 +426,7 @@ def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0
         graph = graph_instance(config)
     imp = Imputation(graph, config)
     plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
-    pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines)
+    pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines, groups=groups)
     slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
     nb = 2 * len(slots) + 1
     pid, did = [line_id(l) for l in plines], [line_id(l) for l in dlines]
