@@ -652,6 +652,37 @@ int grim_match_stats(const grim_match *m, uint64_t out[8]);
 double grim_match_kernel_ms(const grim_match *m);
 void grim_match_free(grim_match *m);
 
+/* Mismatch direction and per-locus grades (csrc/grim_match_grade.h).  Everything of the block above holds -- the flags, the
+ * weights, patient-major results, the donor-row outer fold, the patient-row inner fold, +0.0 starts, no fma, the statistics --
+ * except the per-slot mismatch function and, when graded, the record.  With x1, x2 the patient's fields of a slot, y1, y2 the
+ * donor's and eq(x, y) = x == y and x != 0:
+ *   GRIM_MATCH_DIR_EITHER  mm_s as above
+ *   GRIM_MATCH_DIR_GVH     mm_s = !(eq(x1,y1) || eq(x1,y2)) + !(eq(x2,y1) || eq(x2,y2)): the patient's alleles the donor lacks
+ *                          (graft versus host); both copies are counted, an untyped field is always lacking
+ *   GRIM_MATCH_DIR_HVG     the same with the roles of x and y exchanged: the donor's alleles the patient lacks (host versus graft)
+ *   either == max(gvh, hvg) for all fields, 0 included; so the row pairs with M == 0 under either are among those under gvh
+ *   (and under hvg), and, rounded addition being monotone, mm_gvh[0] >= mm_either[0] and mm_hvg[0] >= mm_either[0] exactly.
+ * Graded record: grade[s][g] is the two-level fold of locus[s] with the condition mm_s == g in the place of mm_s == 0, 0.0 for
+ * s outside K.  mm[] is bit-identical to the ungraded record of the same direction and grade[s][0] to its locus[s].  A pair
+ * that is not computed is all zero bytes.  The result buffer is sized by the record in use; GRIM_MATCH_MAX_PAIRS is the same
+ * for both: a full graded run is 3.25 GiB of result records. */
+#define GRIM_MATCH_DIR_EITHER 0
+#define GRIM_MATCH_DIR_GVH 1
+#define GRIM_MATCH_DIR_HVG 2
+typedef struct {
+  double mm[2 * GRIM_MAXL + 1]; /* mm[m]: probability of m mismatching alleles over K */
+  double grade[GRIM_MAXL][3];   /* grade[s][g]: probability of exactly g mismatches at slot s */
+} grim_match_grade_rec; /* 208 bytes */
+/* grim_match_create is this with (GRIM_MATCH_DIR_EITHER, 0): that matcher runs the kernel it always ran.  NULL with a
+ * grim_last_error text when direction is above GRIM_MATCH_DIR_HVG.  graded: not 0 = the records are grim_match_grade_rec. */
+grim_match *grim_match_create_ex(grim_ctx *ctx, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t direction,
+                                 int graded);
+/* grim_match_results of a graded matcher.  Each of the two answers -3 with a text on a matcher of the other kind, and as
+ * every refusal leaves no results (donors 0, statistics 0, kernel_ms 0; the patients stay). */
+int grim_match_results_graded(grim_match *m, grim_match_grade_rec *out, uint8_t *patient_flags, uint8_t *donor_flags);
+uint32_t grim_match_direction(const grim_match *m); /* as created */
+int grim_match_graded(const grim_match *m);         /* 1 or 0, as created */
+
 /* ======================= donor search: each patient's best N donors (csrc/grim_search.h) ================================
  * The match records above, computed run by run, and on the device a selection of every patient's first top_n donors over all
  * runs: only patients x top_n hits come down, once, however many donor runs were streamed.
@@ -684,6 +715,12 @@ typedef struct grim_search grim_search;
 /* NULL with a grim_last_error text when top_n is 0 or above GRIM_SEARCH_MAX_N, min_p0 is NaN or GRIM_SEARCH_TILE is not as
  * above */
 grim_search *grim_search_create(grim_ctx *ctx, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n, double min_p0);
+/* grim_search_create is this with GRIM_MATCH_DIR_EITHER.  The search owns an ungraded matcher of that direction (NULL with a
+ * text when it is above GRIM_MATCH_DIR_HVG); candidates, threshold and order are the ones above on the directed mm[0] and
+ * mm[1], and the hits hold the directed records.  The merge door cannot know the direction of a list it is given: lists of
+ * one direction are the caller's duty, as distinct ids are. */
+grim_search *grim_search_create_ex(grim_ctx *ctx, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n,
+                                   double min_p0, uint32_t direction);
 /* as grim_match_set_patients; also empties the hit lists and the summed statistics */
 int grim_search_set_patients(grim_search *s, const grim_subject_result *res, uint32_t n, const grim_row *rows, uint32_t n_rows);
 /* empties the hit lists and the summed statistics; the patients stay */

@@ -25,6 +25,7 @@
 #include "grim_refresh.h"
 #include "grim_marginal.h"
 #include "grim_match.h"
+#include "grim_match_grade.h"
 #include "grim_search.h"
 #include "grim_groups.h"
 #include "grim_engine_internal.h"
@@ -2866,6 +2867,8 @@ struct MtBuf {  // one side on the device
 struct grim_match {
   grim_ctx *ctx;
   uint32_t keep_mask;
+  uint32_t direction;  // GRIM_MATCH_DIR_*
+  bool graded;         // records are grim_match_grade_rec
   EmLimits lim;
   DevBuf<unsigned long long> d_stat;
   MtBuf P, D;
@@ -2883,15 +2886,27 @@ struct grim_match {
   double last_ms;
 };
 
-extern "C" grim_match *grim_match_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL]) {
+static_assert(MT_DIR_EITHER == GRIM_MATCH_DIR_EITHER && MT_DIR_GVH == GRIM_MATCH_DIR_GVH && MT_DIR_HVG == GRIM_MATCH_DIR_HVG,
+              "the directions of grim_match_grade.h and of grim_hip.h have drifted apart");
+static_assert(sizeof(grim_match_rec) == 8 * MT_REC && sizeof(grim_match_grade_rec) == 8 * MT_GRADE_REC,
+              "the match records and the kernels' bin counts have drifted apart");
+
+extern "C" grim_match *grim_match_create_ex(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t direction,
+                                            int graded) {
   if (!c || !n_alleles) {
     set_err(c, "grim_match_create: bad arguments");
+    return nullptr;
+  }
+  if (direction > GRIM_MATCH_DIR_HVG) {
+    set_err(c, "grim_match_create: direction must be GRIM_MATCH_DIR_EITHER, _GVH or _HVG");
     return nullptr;
   }
   use_device(c->device);
   grim_match *m = new grim_match();
   m->ctx = c;
   m->keep_mask = keep_mask;
+  m->direction = direction;
+  m->graded = graded != 0;
   for (int q = 0; q < GRIM_MAXL; ++q) m->lim.n_alleles[q] = n_alleles[q];
   if (!m->d_stat.reserve(MT_S_COUNT * MT_S_SLICES) || !m->ev.create()) {
     (void)hipGetLastError();
@@ -2901,6 +2916,13 @@ extern "C" grim_match *grim_match_create(grim_ctx *c, uint32_t keep_mask, const 
   }
   return m;
 }
+
+extern "C" grim_match *grim_match_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL]) {
+  return grim_match_create_ex(c, keep_mask, n_alleles, GRIM_MATCH_DIR_EITHER, 0);
+}
+
+extern "C" uint32_t grim_match_direction(const grim_match *m) { return m ? m->direction : 0; }
+extern "C" int grim_match_graded(const grim_match *m) { return m && m->graded ? 1 : 0; }
 
 extern "C" void grim_match_free(grim_match *m) {
   if (!m) return;
@@ -2990,6 +3012,28 @@ extern "C" int grim_match_set_groups(grim_match *m, const grim_groups *g) {
   return m->gp.attach(c, "grim_match_set_groups", g);
 }
 
+// the pair kernel of the matcher's direction and record: (either, ungraded) is mt_pair_kernel itself
+template <int DIR, bool GRADED>
+static void mt_launch_dir(hipStream_t st, const MtSide &P, uint32_t n_p, uint32_t p0, uint32_t np, const MtSide &D, uint32_t n,
+                          uint32_t keep_mask, double *out, unsigned long long *stat) {
+  hipLaunchKernelGGL((mt_pair_dir_kernel<DIR, GRADED>), dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, keep_mask, out, stat);
+}
+
+static void mt_launch(const grim_match *m, hipStream_t st, const MtSide &P, uint32_t n_p, uint32_t p0, uint32_t np, const MtSide &D,
+                      uint32_t n, double *out, unsigned long long *stat) {
+  const uint32_t k = m->keep_mask;
+  switch (m->direction * 2u + (m->graded ? 1u : 0u)) {
+    case 0: hipLaunchKernelGGL(mt_pair_kernel, dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, k, out, stat); break;
+    case 1: mt_launch_dir<MT_DIR_EITHER, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
+    case 2: mt_launch_dir<MT_DIR_GVH, false>(st, P, n_p, p0, np, D, n, k, out, stat); break;
+    case 3: mt_launch_dir<MT_DIR_GVH, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
+    case 4: mt_launch_dir<MT_DIR_HVG, false>(st, P, n_p, p0, np, D, n, k, out, stat); break;
+    default: mt_launch_dir<MT_DIR_HVG, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
+  }
+}
+
+static uint32_t mt_rec_doubles(const grim_match *m) { return m->graded ? MT_GRADE_REC : MT_REC; }
+
 // donors (device arrays) against the patients set
 static int mt_run(grim_match *m, const char *who, const grim_subject_result *res, const grim_row *rows, uint32_t n, uint32_t rows_used) {
   grim_ctx *c = m->ctx;
@@ -2997,7 +3041,8 @@ static int mt_run(grim_match *m, const char *who, const grim_subject_result *res
   if (n == 0) return 0;
   const uint32_t n_p = m->P.n;
   const uint64_t pairs = (uint64_t)n_p * n;
-  if (!m->d_out.reserve((pairs + 1) * MT_REC)) {  // never an empty allocation
+  const uint64_t rec = mt_rec_doubles(m);
+  if (!m->d_out.reserve((pairs + 1) * rec)) {  // never an empty allocation
     set_err(c, std::string(who) + ": device allocation failed");
     return -1;
   }
@@ -3005,10 +3050,10 @@ static int mt_run(grim_match *m, const char *who, const grim_subject_result *res
   HIPCHK(hipEventRecord(m->ev[0], st), c, -1);
   if (mt_prepare(m, who, m->D, 1u, res, rows, n, rows_used) != 0) return -1;
   if (pairs) {
-    HIPCHK(hipMemsetAsync(m->d_out, 0, sizeof(double) * MT_REC * pairs, st), c, -1);  // a pair that is not computed reads as zero bytes
+    HIPCHK(hipMemsetAsync(m->d_out, 0, sizeof(double) * rec * pairs, st), c, -1);  // a pair that is not computed reads as zero bytes
     const MtSide P = m->P.side(), D = m->D.side();
     for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
-      hipLaunchKernelGGL(mt_pair_kernel, dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, m->keep_mask, m->d_out, m->d_stat);
+      mt_launch(m, st, P, n_p, p0, np, D, n, m->d_out, m->d_stat);
     });
     HIPCHK(hipGetLastError(), c, -1);
   }
@@ -3060,15 +3105,35 @@ extern "C" uint32_t grim_match_patients(const grim_match *m) { return m ? m->P.n
 extern "C" uint32_t grim_match_donors(const grim_match *m) { return m ? m->n_donors : 0; }
 extern "C" double grim_match_kernel_ms(const grim_match *m) { return m ? m->last_ms : 0.0; }
 
-extern "C" int grim_match_results(grim_match *m, grim_match_rec *out, uint8_t *patient_flags, uint8_t *donor_flags) {
-  if (!m) return -1;
+// the records (of `bytes` each) and the flags of the last run
+static int mt_results(grim_match *m, void *out, size_t bytes, uint8_t *patient_flags, uint8_t *donor_flags) {
   grim_ctx *c = m->ctx;
   use_device(c->device);
   const uint64_t pairs = (uint64_t)m->P.n * m->n_donors;
-  if (out && pairs) HIPCHK(hipMemcpy(out, m->d_out, sizeof(grim_match_rec) * pairs, hipMemcpyDeviceToHost), c, -1);
+  if (out && pairs) HIPCHK(hipMemcpy(out, m->d_out, bytes * pairs, hipMemcpyDeviceToHost), c, -1);
   if (patient_flags && m->P.n) HIPCHK(hipMemcpy(patient_flags, m->P.flags, m->P.n, hipMemcpyDeviceToHost), c, -1);
   if (donor_flags && m->n_donors) HIPCHK(hipMemcpy(donor_flags, m->D.flags, m->n_donors, hipMemcpyDeviceToHost), c, -1);
   return 0;
+}
+
+extern "C" int grim_match_results(grim_match *m, grim_match_rec *out, uint8_t *patient_flags, uint8_t *donor_flags) {
+  if (!m) return -1;
+  if (m->graded) {  // the buffer holds records of another size
+    mt_clear(m);
+    refuse(m->ctx, "grim_match_results", "the matcher is graded (call grim_match_results_graded)");
+    return -3;
+  }
+  return mt_results(m, out, sizeof(grim_match_rec), patient_flags, donor_flags);
+}
+
+extern "C" int grim_match_results_graded(grim_match *m, grim_match_grade_rec *out, uint8_t *patient_flags, uint8_t *donor_flags) {
+  if (!m) return -1;
+  if (!m->graded) {
+    mt_clear(m);
+    refuse(m->ctx, "grim_match_results_graded", "the matcher is not graded (call grim_match_results)");
+    return -3;
+  }
+  return mt_results(m, out, sizeof(grim_match_grade_rec), patient_flags, donor_flags);
 }
 
 extern "C" int grim_match_stats(const grim_match *m, uint64_t out[8]) {
@@ -3109,8 +3174,8 @@ static void sr_empty(grim_search *s) {
   s->select_ms = s->kernel_ms = 0.0;
 }
 
-extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n,
-                                           double min_p0) {
+extern "C" grim_search *grim_search_create_ex(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n,
+                                              double min_p0, uint32_t direction) {
   if (!c || !n_alleles) {
     set_err(c, "grim_search_create: bad arguments");
     return nullptr;
@@ -3133,7 +3198,7 @@ extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, cons
     }
     tile = (uint32_t)v;
   }
-  grim_match *m = grim_match_create(c, keep_mask, n_alleles);
+  grim_match *m = grim_match_create_ex(c, keep_mask, n_alleles, direction, 0);  // ungraded: the selection reads 128-byte records
   if (!m) return nullptr;
   use_device(c->device);
   grim_search *s = new grim_search();
@@ -3149,6 +3214,11 @@ extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, cons
     return nullptr;
   }
   return s;
+}
+
+extern "C" grim_search *grim_search_create(grim_ctx *c, uint32_t keep_mask, const uint32_t n_alleles[GRIM_MAXL], uint32_t top_n,
+                                           double min_p0) {
+  return grim_search_create_ex(c, keep_mask, n_alleles, top_n, min_p0, GRIM_MATCH_DIR_EITHER);
 }
 
 extern "C" void grim_search_free(grim_search *s) {

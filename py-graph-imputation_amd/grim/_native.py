@@ -671,10 +671,14 @@ class MarginalReducer(_Handle):
 EXPORTS += [
     "grim_match_create", "grim_match_set_patients", "grim_match_run", "grim_match_run_records", "grim_match_patients",
     "grim_match_donors", "grim_match_results", "grim_match_stats", "grim_match_kernel_ms", "grim_match_free",
+    "grim_match_create_ex", "grim_match_results_graded", "grim_match_direction", "grim_match_graded",
 ]
 
 MATCH_DT = np.dtype([("mm", "<f8", (2 * MAXL + 1,)), ("locus", "<f8", (MAXL,))])
 assert MATCH_DT.itemsize == 128
+MATCH_GRADE_DT = np.dtype([("mm", "<f8", (2 * MAXL + 1,)), ("grade", "<f8", (MAXL, 3))])  # grim_match_grade_rec
+assert MATCH_GRADE_DT.itemsize == 208
+MATCH_DIR_EITHER, MATCH_DIR_GVH, MATCH_DIR_HVG = 0, 1, 2
 MATCH_STATS = ("patients_valid", "donors_valid", "patients_private", "donors_private", "undefined", "pairs", "row_pairs")
 MATCH_VALID, MATCH_PRIVATE, MATCH_UNDEFINED = 1, 2, 4
 MATCH_MAX_PAIRS = 1 << 24
@@ -705,6 +709,14 @@ def _match_lib():
         L.grim_match_kernel_ms.restype = C.c_double
         L.grim_match_kernel_ms.argtypes = [C.c_void_p]
         L.grim_match_free.argtypes = [C.c_void_p]
+        L.grim_match_create_ex.restype = C.c_void_p
+        L.grim_match_create_ex.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int]
+        L.grim_match_results_graded.restype = C.c_int
+        L.grim_match_results_graded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.grim_match_direction.restype = C.c_uint32
+        L.grim_match_direction.argtypes = [C.c_void_p]
+        L.grim_match_graded.restype = C.c_int
+        L.grim_match_graded.argtypes = [C.c_void_p]
         _match_ready = True
     return L
 
@@ -712,18 +724,28 @@ def _match_lib():
 class Matcher(_Handle):
     """grim_match: for every (patient, donor) pair the probabilities of 0, 1, 2, ... mismatching alleles over the kept locus
     slots and the per-locus match probabilities, on the device (include/grim_hip.h, the grim_match_* block).  The patients
-    stay set across runs; results(), stats() and kernel_ms() speak of the last run."""
+    stay set across runs; results(), stats() and kernel_ms() speak of the last run.  `direction`: MATCH_DIR_EITHER, _GVH or
+    _HVG, the per-locus mismatch function; `graded`: the records are MATCH_GRADE_DT and come from results_graded()."""
 
     _free = "grim_match_free"
 
-    def __init__(self, ctx, keep_mask, n_alleles):
+    def __init__(self, ctx, keep_mask, n_alleles, direction=0, graded=False):
         L = _match_lib()
         self.ctx = ctx
         counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
         arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
-        self.h = L.grim_match_create(ctx.h, int(keep_mask), arr)
+        direction = int(direction)
+        if not 0 <= direction < 1 << 32:
+            raise ValueError("direction out of range")
+        self.h = L.grim_match_create_ex(ctx.h, int(keep_mask), arr, direction, 1 if graded else 0)
         if not self.h:
             raise NativeError("grim_match_create failed: " + ctx.error())
+
+    def direction(self):
+        return int(_match_lib().grim_match_direction(self.h))
+
+    def graded(self):
+        return bool(_match_lib().grim_match_graded(self.h))
 
     def set_groups(self, groups):
         """a Groups map for everything that follows (None detaches); drops the patients and the last results"""
@@ -758,6 +780,15 @@ class Matcher(_Handle):
                                                     _ptr(df) if n_d else None), "grim_match_results", code=False)
         return out, pf, df
 
+    def results_graded(self):
+        """of a graded matcher -> (records MATCH_GRADE_DT[patients][donors], patient flags, donor flags)"""
+        n_p, n_d = self.patients(), self.donors()
+        out = np.zeros((n_p, n_d), dtype=MATCH_GRADE_DT)
+        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
+        self._check(_match_lib().grim_match_results_graded(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
+                                                           _ptr(df) if n_d else None), "grim_match_results_graded", code=False)
+        return out, pf, df
+
     def stats(self):
         out = (C.c_uint64 * 8)()
         _match_lib().grim_match_stats(self.h, out)
@@ -772,6 +803,7 @@ EXPORTS += [
     "grim_search_create", "grim_search_set_patients", "grim_search_reset", "grim_search_run", "grim_search_run_records",
     "grim_search_results", "grim_search_flags", "grim_search_patients", "grim_search_donors", "grim_search_top_n",
     "grim_search_stats", "grim_search_kernel_ms", "grim_search_select_ms", "grim_search_free", "grim_search_merge_hits",
+    "grim_search_create_ex",
 ]
 
 SEARCH_DT = np.dtype([("donor", "<u4"), ("reserved", "<u4"), ("rec", MATCH_DT)])
@@ -814,6 +846,8 @@ def _search_lib():
         L.grim_search_free.argtypes = [C.c_void_p]
         L.grim_search_merge_hits.restype = C.c_int
         L.grim_search_merge_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.grim_search_create_ex.restype = C.c_void_p
+        L.grim_search_create_ex.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_double, C.c_uint32]
         _search_ready = True
     return L
 
@@ -822,11 +856,11 @@ class Searcher(_Handle):
     """grim_search: every patient's first top_n donors by match probability (mm[0] down, then mm[1] down, then id up) among the
     pairs with mm[0] >= min_p0, over all runs since the patients were set or the search was reset, selected on the device
     (include/grim_hip.h, the grim_search_* block).  results() and stats() speak of all runs so far; flags(), donors(),
-    kernel_ms() and select_ms() of the last one."""
+    kernel_ms() and select_ms() of the last one.  `direction`: as Matcher; order and threshold are on the directed mm[0], mm[1]."""
 
     _free = "grim_search_free"
 
-    def __init__(self, ctx, keep_mask, n_alleles, top_n, min_p0=0.0):
+    def __init__(self, ctx, keep_mask, n_alleles, top_n, min_p0=0.0, direction=0):
         L = _search_lib()
         self.ctx = ctx
         counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
@@ -834,7 +868,10 @@ class Searcher(_Handle):
         top_n = int(top_n)
         if not 0 <= top_n < 1 << 32:
             raise ValueError("top_n out of range")
-        self.h = L.grim_search_create(ctx.h, int(keep_mask), arr, top_n, float(min_p0))
+        direction = int(direction)
+        if not 0 <= direction < 1 << 32:
+            raise ValueError("direction out of range")
+        self.h = L.grim_search_create_ex(ctx.h, int(keep_mask), arr, top_n, float(min_p0), direction)
         if not self.h:
             raise NativeError("grim_search_create failed: " + ctx.error())
 

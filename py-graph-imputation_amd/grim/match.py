@@ -16,6 +16,11 @@ The reference ends at the printed `.umug` files; the operation is defined here (
           H[m] += ph[m],  L[locus] += pl[locus]
       mm[m] = H[m],  locus[s] = L[s]
 
+Two keywords change what is counted, not how it is summed.  `direction`: "either" is the mm above; "gvh" counts
+the patient's alleles the donor lacks, mm = !(eq(x1,y1) or eq(x1,y2)) + !(eq(x2,y1) or eq(x2,y2)), an untyped allele always
+lacking; "hvg" the donor's alleles the patient lacks; either = max(gvh, hvg).  `graded`: the record holds, in the place of
+locus[s], grade[s][g] for g = 0, 1, 2: the same fold with `mm == g` for `mm == 0` (nat.MATCH_GRADE_DT).
+
 `match_probabilities` runs it on the device, on the rows the donors' batches leave in HBM (csrc/grim_match.h).  Pairs in
 which a subject holds an allele the dictionary does not know are left out by the device (the allele's id is private to the
 subject) and folded here on allele text.  `match_records` is the same fold over record arrays in plain Python floats, laid
@@ -31,6 +36,36 @@ from . import _native as nat
 from .blocks import Blocks, note_unsupported, read_lines
 from .groups import as_groups, regroup_umug_text
 from .marginal import keep_mask as _keep_mask
+
+
+DIRECTIONS = {"either": nat.MATCH_DIR_EITHER, "gvh": nat.MATCH_DIR_GVH, "hvg": nat.MATCH_DIR_HVG}
+
+
+def direction_code(direction):
+    """one of "either", "gvh", "hvg" (or its nat.MATCH_DIR_* number) -> the number"""
+    if isinstance(direction, str) and direction in DIRECTIONS:
+        return DIRECTIONS[direction]
+    if isinstance(direction, (int, np.integer)) and not isinstance(direction, bool) and int(direction) in DIRECTIONS.values():
+        return int(direction)
+    raise ValueError("direction must be one of %s, not %r" % (", ".join(sorted(DIRECTIONS)), direction))
+
+
+def locus_mismatches(x1, x2, y1, y2, direction=nat.MATCH_DIR_EITHER):
+    """mm_s of DESIGN 4.7 / 4.12 on allele numbers (0 = untyped), integers or integer arrays that broadcast: the patient's
+    x1, x2 against the donor's y1, y2.  either: 2 - the better pairing; gvh: the patient's alleles the donor lacks; hvg: the
+    donor's alleles the patient lacks."""
+    def eq(x, y):
+        return (x == y) & (x != 0)
+
+    if direction == nat.MATCH_DIR_EITHER:
+        straight = eq(x1, y1) * 1 + eq(x2, y2) * 1
+        crossed = eq(x1, y2) * 1 + eq(x2, y1) * 1
+        return 2 - np.maximum(straight, crossed)
+    if direction == nat.MATCH_DIR_HVG:
+        x1, x2, y1, y2 = y1, y2, x1, x2
+    elif direction != nat.MATCH_DIR_GVH:
+        raise ValueError("not a direction: %r" % (direction,))
+    return 2 - ((eq(x1, y1) | eq(x1, y2)) * 1 + (eq(x2, y1) | eq(x2, y2)) * 1)
 
 
 class _Folder:
@@ -53,23 +88,25 @@ class _Folder:
                 y[k, r] = ids.setdefault(b, len(ids))
         return x, y
 
-    def fold(self, pg, pw, dg, dv):
-        """patient rows (packed genotypes pg, weights pw) against donor rows (dg, dv) -> (H[2 nk + 1], L[nk])"""
+    def fold(self, pg, pw, dg, dv, direction=nat.MATCH_DIR_EITHER, graded=False):
+        """patient rows (packed genotypes pg, weights pw) against donor rows (dg, dv) under `direction` (a nat.MATCH_DIR_*)
+        -> (H[2 nk + 1], L[nk]); graded: (H, G[nk][3]), G[k][g] the fold of L[k] with `mm == g` in the place of `mm == 0`"""
         nk = self.nk
         nb = 2 * nk + 1
+        grades = (0, 1, 2) if graded else (0,)
         n_p, n_d = len(pw), len(dv)
         M = np.zeros((n_d, n_p), dtype=np.int64)  # M[j][i]
-        zero = []  # per kept locus and donor row: the patient rows without a mismatch there, ascending
+        at = []  # per kept locus and grade, per donor row: the patient rows with that many mismatches there, ascending
         for k in range(nk):
-            x1, x2, y1, y2 = pg[0][k][None, :], pg[1][k][None, :], dg[0][k][:, None], dg[1][k][:, None]
-            straight = ((x1 == y1) & (x1 != 0)).astype(np.int64) + ((x2 == y2) & (x2 != 0))
-            crossed = ((x1 == y2) & (x1 != 0)).astype(np.int64) + ((x2 == y1) & (x2 != 0))
-            mm = 2 - np.maximum(straight, crossed)
+            mm = locus_mismatches(pg[0][k][None, :], pg[1][k][None, :], dg[0][k][:, None], dg[1][k][:, None], direction)
             M += mm
-            jj, ii = np.nonzero(mm == 0)
-            zero.append((np.searchsorted(jj, np.arange(n_d + 1)).tolist(), ii.tolist()))
+            per = []
+            for g in grades:
+                jj, ii = np.nonzero(mm == g)
+                per.append((np.searchsorted(jj, np.arange(n_d + 1)).tolist(), ii.tolist()))
+            at.append(per)
         M = M.tolist()
-        H, L = [0.0] * nb, [0.0] * nk
+        H, G = [0.0] * nb, [[0.0] * len(grades) for _ in range(nk)]
         for j in range(n_d):
             v = dv[j]
             ts = [w * v for w in pw]
@@ -79,12 +116,12 @@ class _Folder:
             for m in range(nb):
                 H[m] = H[m] + ph[m]
             for k in range(nk):
-                bounds, ii = zero[k]
-                pl = 0.0
-                for i in ii[bounds[j]:bounds[j + 1]]:
-                    pl = pl + ts[i]
-                L[k] = L[k] + pl
-        return H, L
+                for g, (bounds, ii) in enumerate(at[k]):
+                    pl = 0.0
+                    for i in ii[bounds[j]:bounds[j + 1]]:
+                        pl = pl + ts[i]
+                    G[k][g] = G[k][g] + pl
+        return H, (G if graded else [row[0] for row in G])
 
 
 def _total(ps):
@@ -102,10 +139,11 @@ def _slots_of(keep_mask):
 
 
 def _store(rec, slots, H, L):
-    """H, L of a pair into one nat.MATCH_DT record"""
+    """H, L of a pair into one nat.MATCH_DT record, or H, G into one nat.MATCH_GRADE_DT record"""
     rec["mm"][:len(H)] = H
+    field = "grade" if "grade" in rec.dtype.names else "locus"
     for k, s in enumerate(slots):
-        rec["locus"][s] = L[k]
+        rec[field][s] = L[k]
 
 
 def _side(res, rows, slots, n_alleles, folder):
@@ -139,13 +177,16 @@ def _side(res, rows, slots, n_alleles, folder):
     return flags, subs
 
 
-def match_records(pres, prows, dres, drows, keep_mask, n_alleles, groups=None):
+def match_records(pres, prows, dres, drows, keep_mask, n_alleles, groups=None, direction="either", graded=False):
     """The fold on record arrays (nat.RESULT_DT / nat.ROW_DT of the patients and of the donors) as grim_match_run_records
     defines it (include/grim_hip.h) -> (records nat.MATCH_DT[P][D], patient flags, donor flags, stats), laid out as the device
     lays them out: a pair that is not computed is a record of zeros; without donors every statistic is 0.  `groups`: an
     AlleleGroups (grim.groups) whose n_alleles are the ones given: both sides' rows are mapped first and n_groups stands in
-    the place of n_alleles, as on the device with the map attached."""
+    the place of n_alleles, as on the device with the map attached.  `direction`: "either", "gvh" (the patient's alleles the
+    donor lacks) or "hvg" (the donor's alleles the patient lacks), the per-locus mismatch function; `graded`:
+    the records are nat.MATCH_GRADE_DT, per locus the probabilities of exactly 0, 1 and 2 mismatches."""
     slots = _slots_of(keep_mask)
+    direction = direction_code(direction)
     n_alleles = [int(x) for x in n_alleles] + [0] * (nat.MAXL - len(n_alleles))
     if groups is not None:
         if list(groups.n_alleles) != n_alleles:
@@ -154,7 +195,7 @@ def match_records(pres, prows, dres, drows, keep_mask, n_alleles, groups=None):
     folder = _Folder(len(slots))
     pflags, psubs = _side(pres, prows, slots, n_alleles, folder)
     dflags, dsubs = _side(dres, drows, slots, n_alleles, folder)
-    out = np.zeros((len(pres), len(dres)), dtype=nat.MATCH_DT)
+    out = np.zeros((len(pres), len(dres)), dtype=nat.MATCH_GRADE_DT if graded else nat.MATCH_DT)
     stats = dict.fromkeys(nat.MATCH_STATS, 0)
     if len(dres) == 0:
         return out, pflags, dflags, stats
@@ -169,7 +210,7 @@ def match_records(pres, prows, dres, drows, keep_mask, n_alleles, groups=None):
         for d, ds in enumerate(dsubs):
             if (dflags[d] & ready) != nat.MATCH_VALID:
                 continue
-            H, L = folder.fold(ps[0], ps[1], ds[0], ds[1])
+            H, L = folder.fold(ps[0], ps[1], ds[0], ds[1], direction, graded)
             _store(out[p, d], slots, H, L)
             stats["pairs"] += 1
             stats["row_pairs"] += len(ps[1]) * len(ds[1])
@@ -206,13 +247,15 @@ def _text_subjects(text, keep):
     return subs
 
 
-def match_umug_text(patient_text, donor_text, keep_loci, loci=None, groups=None):
+def match_umug_text(patient_text, donor_text, keep_loci, loci=None, groups=None, direction="either", graded=False):
     """The fold on `.umug` text in `id,genotype,p,rank` form -> (patient ids, donor ids, records[P][D]); a record is
     (mm[0..2|K|], {locus name: probability of no mismatch}).  A subject is the run of rows from one rank 0 to the next; a
     `^`-part of a genotype belongs to the locus named before its first `*`, its two alleles are the `+`-separated texts; a
     kept locus a row lacks is untyped; two alleles are equal when their texts are.  `loci`: the names that may be kept (an
     unknown one raises); `groups`: a group specification (grim.groups.GroupSpec or what it takes): both texts go through
-    `regroup_umug_text` first."""
+    `regroup_umug_text` first.  `direction`: as `match_records`; `graded`: a record is (mm[0..2|K|], {locus name: [the
+    probabilities of exactly 0, 1 and 2 mismatches]})."""
+    direction = direction_code(direction)
     if groups is not None:
         patient_text, donor_text = regroup_umug_text(patient_text, groups), regroup_umug_text(donor_text, groups)
     keep = [keep_loci] if isinstance(keep_loci, str) else list(dict.fromkeys(keep_loci))
@@ -235,20 +278,22 @@ def match_umug_text(patient_text, donor_text, keep_loci, loci=None, groups=None)
     for _, pg, pw in sides[0]:
         line = []
         for _, dg, dv in sides[1]:
-            H, L = folder.fold(pg, pw, dg, dv)
+            H, L = folder.fold(pg, pw, dg, dv, direction, graded)
             line.append((H, dict(zip(keep, L))))
         records.append(line)
     return [s[0] for s in sides[0]], [s[0] for s in sides[1]], records
 
 
-def text_records_array(records, locus_slot):
-    """records of match_umug_text -> nat.MATCH_DT[P][D]; `locus_slot`: name -> slot (Graph.locus_slot)"""
-    out = np.zeros((len(records), len(records[0]) if records else 0), dtype=nat.MATCH_DT)
+def text_records_array(records, locus_slot, graded=False):
+    """records of match_umug_text -> nat.MATCH_DT[P][D] (nat.MATCH_GRADE_DT of its graded records); `locus_slot`: name -> slot
+    (Graph.locus_slot)"""
+    out = np.zeros((len(records), len(records[0]) if records else 0), dtype=nat.MATCH_GRADE_DT if graded else nat.MATCH_DT)
+    field = "grade" if graded else "locus"
     for p, line in enumerate(records):
         for d, (H, L) in enumerate(line):
             out[p, d]["mm"][:len(H)] = H
             for name, v in L.items():
-                out[p, d]["locus"][int(locus_slot[name])] = v
+                out[p, d][field][int(locus_slot[name])] = v
     return out
 
 
@@ -257,8 +302,10 @@ class _Pairing:
     Matcher or a Searcher), the donors cut into blocks, the check of a block's flags, and the host fold of the pairs the
     device leaves out.  The callers run each donor block themselves and do what they like with the pairs."""
 
-    def __init__(self, imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups=None):
+    def __init__(self, imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups=None,
+                 direction="either", graded=False):
         self.imputation = imputation
+        self.direction, self.graded = direction_code(direction), bool(graded)  # of the text route, as of the device object
         self.g = g = imputation.netGraph
         self.groups = as_groups(g, groups)  # None: alleles compare as the dictionary has them
         self.mask = _keep_mask(g.locus_slot, keep_loci)
@@ -316,7 +363,7 @@ class _Pairing:
 
     def host_pairs(self, block, df):
         """a donor block after its run, `df` its flags: checks it, then yields (p, d, H, L) for every pair of valid subjects
-        the device left out for a private allele: the same fold on allele text"""
+        the device left out for a private allele: the same fold on allele text (L is G[nk][3] when graded)"""
         self.check(block, df)
         ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
         pf, ptext, dtext = self.pf, self.ptext, {}
@@ -328,7 +375,7 @@ class _Pairing:
                     ptext[p] = self._text_subject(self.pblock, int(p))
                 if d not in dtext:
                     dtext[d] = self._text_subject(block, int(d))
-                H, L = self.folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1])
+                H, L = self.folder.fold(ptext[p][0], ptext[p][1], dtext[d][0], dtext[d][1], self.direction, self.graded)
                 yield p, d, H, L
 
     def _text_subject(self, block, i):
@@ -362,7 +409,7 @@ class _Pairing:
 
 
 def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines=65536, planb=None, em=False,
-                        groups=None):
+                        groups=None, direction="either", graded=False):
     """Match probabilities of every patient against every donor on the device.  `patient_lines`: input lines;
     `donor_lines_or_path`: input lines (a list) or the path of an input file; `config`: the configuration dict of
     `load_config`; `keep_loci`: locus names of its loci_map.  The patients are imputed as one device batch, their records
@@ -374,21 +421,26 @@ def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, 
     `host_pairs` (pairs folded on text).  The cuts do not show in any byte.  Subjects the device cannot answer follow
     `imputation.on_unsupported` as in `impute_lines_block`.  `groups`: an AlleleGroups of the imputation's graph or a group
     specification (grim.groups): alleles are equal when their groups are -- on the device by group id, in the pairs folded
-    here by group name -- and the result equals `match_umug_text` on the regrouped text."""
-    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups)
-    matcher = nat.Matcher(pairing.ctx, pairing.mask, pairing.n_alleles)
+    here by group name -- and the result equals `match_umug_text` on the regrouped text.  `direction`, `graded`: as
+    `match_records`, on the device (csrc/grim_match_grade.h) and in the pairs folded here; graded, records is
+    nat.MATCH_GRADE_DT."""
+    pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups, direction,
+                       graded)
+    graded = pairing.graded
+    matcher = nat.Matcher(pairing.ctx, pairing.mask, pairing.n_alleles, pairing.direction, graded)
+    results = matcher.results_graded if graded else matcher.results
     stats = dict.fromkeys(nat.MATCH_STATS, 0)
     stats.update(blocks=0, kernel_ms=0.0, host_pairs=0)
-    out = np.zeros((len(pairing.plines), len(pairing.dlines)), dtype=nat.MATCH_DT)
+    out = np.zeros((len(pairing.plines), len(pairing.dlines)), dtype=nat.MATCH_GRADE_DT if graded else nat.MATCH_DT)
     donor_ok = np.zeros(len(pairing.dlines), dtype=bool)
     try:
-        pairing.set_patients(matcher, lambda: matcher.results()[1], stats)
+        pairing.set_patients(matcher, lambda: results()[1], stats)
         for block in pairing.donor_blocks():
             if block.batch is None:
                 pairing.check(block, np.zeros(0, dtype=np.uint8))
                 continue
             matcher.run(block.batch)
-            rec, _, df = matcher.results()
+            rec, _, df = results()
             run = matcher.stats()
             for p, d, H, L in pairing.host_pairs(block, df):
                 _store(rec[p, d], pairing.slots, H, L)
@@ -412,11 +464,14 @@ def line_id(line):
     return line.split("," if "," in line else "%", 1)[0]
 
 
-def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0=0.0, block_lines=65536, groups=None):
+def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0=0.0, block_lines=65536, groups=None,
+               direction="either", graded=False):
     """The configuration's input file as donors against the input file `patients_path`, on `graph` (built from the
     configuration's graph CSVs when None) -> a CSV at `out_path`: a header `patient_id,donor_id,mm0,...,mm{2|K|},<kept locus
     names>`, then one line per computed pair with mm0 >= min_p0, patient-major, floats written with repr.  Paths are taken
-    as the configuration gives them.  `groups`: as `match_probabilities`.  -> stats"""
+    as the configuration gives them.  `groups`, `direction`: as `match_probabilities`.  `graded`: after the kept locus names
+    (the probability of no mismatch there) come `<locus>_mm1,<locus>_mm2` for every kept locus, the probabilities of exactly
+    one and of two mismatches.  -> stats"""
     from .grim import graph_instance
     from .imputation.impute import Imputation
     from .run_impute_def import load_config
@@ -426,16 +481,22 @@ def match_file(conf_file, patients_path, keep_loci, out_path, graph=None, min_p0
         graph = graph_instance(config)
     imp = Imputation(graph, config)
     plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
-    pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines, groups=groups)
+    pok, dok, rec, stats = match_probabilities(imp, plines, dlines, config, keep_loci, block_lines=block_lines, groups=groups,
+                                               direction=direction, graded=graded)
     slots = _slots_of(_keep_mask(graph.locus_slot, keep_loci))
     nb = 2 * len(slots) + 1
     pid, did = [line_id(l) for l in plines], [line_id(l) for l in dlines]
     with open(out_path, "w") as fh:
-        fh.write(",".join(["patient_id", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots]) + "\n")
+        more = ["%s_mm%d" % (graph.slot_locus[s], g) for s in slots for g in (1, 2)] if graded else []
+        fh.write(",".join(["patient_id", "donor_id"] + ["mm%d" % m for m in range(nb)] + [graph.slot_locus[s] for s in slots] + more) + "\n")
         for p in np.flatnonzero(pok):
             for d in np.flatnonzero(dok):
                 r = rec[p, d]
                 if float(r["mm"][0]) >= min_p0:
-                    vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
+                    if graded:
+                        vals = [float(x) for x in r["mm"][:nb]] + [float(r["grade"][s][0]) for s in slots]
+                        vals += [float(r["grade"][s][g]) for s in slots for g in (1, 2)]
+                    else:
+                        vals = [float(x) for x in r["mm"][:nb]] + [float(r["locus"][s]) for s in slots]
                     fh.write("%s,%s,%s\n" % (pid[p], did[d], ",".join(repr(v) for v in vals)))
     return stats

@@ -21,6 +21,10 @@ bit for bit.  There is no CPU fallback of the device functions.
 The first N of a union are among the first N of each part, so hit lists that other searches produced are inputs of the same
 selection: `DonorSearch` is `search_donors` opened once, fed its donors piece by piece and given such lists through the
 device's merge door (`nat.Searcher.merge`); `merge_hit_lists` is that door's twin in plain Python.
+
+`direction` ("either", "gvh", "hvg") chooses the records' mismatch function: candidates, threshold and order are
+the ones above on the directed mm[0] and mm[1].  A hit list does not say under which direction it was made: merging lists of
+one direction only is the caller's duty.
 """
 
 import math
@@ -29,7 +33,7 @@ import numpy as np
 
 from . import _native as nat
 from .blocks import read_lines
-from .match import _Pairing, _keep_mask, _slots_of, _store, line_id, match_records, match_umug_text
+from .match import _Pairing, _keep_mask, _slots_of, _store, direction_code, line_id, match_records, match_umug_text
 
 
 def _check(top_n, min_p0):
@@ -47,20 +51,21 @@ def _empty_hits(n, top_n):
     return hits
 
 
-def search_records(pres, prows, donor_runs, keep_mask, n_alleles, top_n, min_p0, groups=None):
+def search_records(pres, prows, donor_runs, keep_mask, n_alleles, top_n, min_p0, groups=None, direction="either"):
     """The selection on record arrays as grim_search_run_records defines it (include/grim_hip.h).  `donor_runs`: a list of
     (res, rows, ids), nat.RESULT_DT / nat.ROW_DT arrays and one id per donor, distinct over all runs.  Runs `match_records`
     per run, keeps the computed pairs with mm[0] >= min_p0 and sorts them -> (hits nat.SEARCH_DT[P][top_n], n_hits u32[P],
-    stats), laid out as the device lays them out: stats are each run's match statistics summed, and `candidates`.  `groups`:
-    as `match_records`."""
+    stats), laid out as the device lays them out: stats are each run's match statistics summed, and `candidates`.  `groups`,
+    `direction`: as `match_records`."""
     top_n, min_p0 = _check(top_n, min_p0)
+    direction = direction_code(direction)
     ready = nat.MATCH_VALID | nat.MATCH_PRIVATE
     stats = dict.fromkeys(nat.SEARCH_STATS, 0)
     found = [[] for _ in range(len(pres))]  # per patient: (-mm0, -mm1, id, record)
     for res, rows, ids in donor_runs:
         if len(ids) != len(res):
             raise ValueError("%d donors but %d ids" % (len(res), len(ids)))
-        rec, pf, df, run = match_records(pres, prows, res, rows, keep_mask, n_alleles, groups)
+        rec, pf, df, run = match_records(pres, prows, res, rows, keep_mask, n_alleles, groups, direction)
         for k in nat.MATCH_STATS:
             stats[k] += run[k]
         for p in np.flatnonzero((pf & ready) == nat.MATCH_VALID):
@@ -146,12 +151,12 @@ def merge_hit_lists(lists, top_n, min_p0, running=None):
     return out, n_out
 
 
-def search_umug_text(patient_text, donor_text, keep_loci, top_n, min_p0=0.0, groups=None):
+def search_umug_text(patient_text, donor_text, keep_loci, top_n, min_p0=0.0, groups=None, direction="either"):
     """The selection on `.umug` text through `match_umug_text`; a donor's id is its position in the donor text -> (patient ids,
     donor ids, hits): hits[p] is the list of (donor position, mm[0..2|K|], {locus name: probability of no mismatch}) of the
-    patient's first top_n donors with mm[0] >= min_p0, in order.  `groups`: a group specification, as `match_umug_text`."""
+    patient's first top_n donors with mm[0] >= min_p0, in order.  `groups`: a group specification, `direction`: as `match_umug_text`."""
     top_n, min_p0 = _check(top_n, min_p0)
-    pid, did, records = match_umug_text(patient_text, donor_text, keep_loci, groups=groups)
+    pid, did, records = match_umug_text(patient_text, donor_text, keep_loci, groups=groups, direction=direction)
     hits = []
     for line in records:
         cands = [(-H[0], -H[1], d) for d, (H, _) in enumerate(line) if H[0] >= min_p0]
@@ -167,16 +172,16 @@ class DonorSearch:
     `search_donors`, without the donors."""
 
     def __init__(self, imputation, patient_lines, config, keep_loci, top_n, min_p0=0.0, block_lines=65536, planb=None, em=False,
-                 groups=None):
+                 groups=None, direction="either"):
         self.top_n, self.min_p0 = _check(top_n, min_p0)
-        self.pairing = pairing = _Pairing(imputation, patient_lines, None, config, keep_loci, block_lines, planb, em, groups)
+        self.pairing = pairing = _Pairing(imputation, patient_lines, None, config, keep_loci, block_lines, planb, em, groups, direction)
         self.searcher = None
         self.stats = dict.fromkeys(nat.SEARCH_STATS, 0)
         self.stats.update(blocks=0, kernel_ms=0.0, select_ms=0.0, host_pairs=0, download_bytes=0)
         self.merge_ms = 0.0  # device time of the merges
         self.host = {}   # patient -> [((-mm0, -mm1, id), H, L)] of the pairs folded here, at most top_n after a block
         try:
-            self.searcher = nat.Searcher(pairing.ctx, pairing.mask, pairing.n_alleles, self.top_n, self.min_p0)
+            self.searcher = nat.Searcher(pairing.ctx, pairing.mask, pairing.n_alleles, self.top_n, self.min_p0, pairing.direction)
             pairing.set_patients(self.searcher, lambda: self.searcher.flags()[0], self.stats)
         except BaseException:
             self.close()
@@ -274,7 +279,7 @@ class DonorSearch:
 
 
 def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_loci, top_n, min_p0=0.0, block_lines=65536, planb=None,
-                  em=False, groups=None):
+                  em=False, groups=None, direction="either"):
     """Every patient's first `top_n` donors on the device.  Arguments as `match_probabilities`: `patient_lines`: input lines;
     `donor_lines_or_path`: input lines (a list) or the path of an input file; `config`: the configuration dict of
     `load_config`; `keep_loci`: locus names of its loci_map.  The patients are imputed as one device batch and set once; the
@@ -290,9 +295,9 @@ def search_donors(imputation, patient_lines, donor_lines_or_path, config, keep_l
     match statistics as `match_probabilities` sums them, `candidates` (device and host), and `blocks`, `kernel_ms`,
     `select_ms`, `host_pairs` (pairs folded on text) and `download_bytes` (hits and counts fetched from the device).  The cuts
     do not show in any byte.  Subjects the device cannot answer follow `imputation.on_unsupported` as in
-    `impute_lines_block`.  `groups`: as `match_probabilities`."""
+    `impute_lines_block`.  `groups`, `direction`: as `match_probabilities`."""
     top_n, min_p0 = _check(top_n, min_p0)
-    search = DonorSearch(imputation, patient_lines, config, keep_loci, top_n, min_p0, block_lines, planb, em, groups)
+    search = DonorSearch(imputation, patient_lines, config, keep_loci, top_n, min_p0, block_lines, planb, em, groups, direction)
     try:
         search.feed(donor_lines_or_path)
         return search.hits()
@@ -313,11 +318,12 @@ def write_hits_csv(out_path, graph, keep_loci, plines, dlines, pok, hits, n_hits
                 fh.write("%s,%d,%s,%s\n" % (line_id(plines[p]), k, line_id(dlines[int(hits[p, k]["donor"])]), ",".join(repr(v) for v in vals)))
 
 
-def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, graph=None, block_lines=65536, groups=None):
+def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, graph=None, block_lines=65536, groups=None,
+                direction="either"):
     """The configuration's input file as donors against the input file `patients_path`, on `graph` (built from the
     configuration's graph CSVs when None) -> a CSV at `out_path`: a header `patient_id,rank,donor_id,mm0,...,mm{2|K|},<kept
     locus names>`, then per patient its hits in order, ranks from 0, patient-major, floats written with repr.  Paths are
-    taken as the configuration gives them.  `groups`: as `search_donors`.  -> stats"""
+    taken as the configuration gives them.  `groups`, `direction`: as `search_donors`.  -> stats"""
     from .grim import graph_instance
     from .imputation.impute import Imputation
     from .run_impute_def import load_config
@@ -328,6 +334,6 @@ def search_file(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0
     imp = Imputation(graph, config)
     plines, dlines = read_lines(patients_path), read_lines(config["imputation_input_file"])
     pok, hits, n_hits, stats = search_donors(imp, plines, dlines, config, keep_loci, top_n, min_p0=min_p0, block_lines=block_lines,
-                                             groups=groups)
+                                             groups=groups, direction=direction)
     write_hits_csv(out_path, graph, keep_loci, plines, dlines, pok, hits, n_hits)
     return stats

@@ -771,7 +771,7 @@ SEARCH_SUMS = ("donors_valid", "donors_private", "pairs", "row_pairs", "candidat
 
 
 def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk_lines=None, graph=None, compute=None, timeout_s=1800,
-                   block_lines=65536):
+                   block_lines=65536, direction="either"):
     """The donor search (grim.search.search_donors) across the ranks of the torch.distributed job, or alone if there is none:
     the configuration's input file as donors against the input file `patients_path`.  Every rank builds its graph and opens
     one grim.search.DonorSearch over all patients; the ranks pull donor chunks of `chunk_lines` lines from the job's counter
@@ -784,20 +784,23 @@ def search_sharded(conf_file, patients_path, keep_loci, top_n, min_p0=0.0, chunk
     host_pairs) are sums over the ranks and equal `search_donors`'; patients_* and undefined are rank 0's; kernel_ms,
     select_ms, blocks and download_bytes are summed; `chunks`, `merge_ms` (device time of rank 0's merge) and `unsupported`
     (the donor subjects of all ranks, by input line, that GRIM_ON_UNSUPPORTED=skip let the job go on without) are added, and
-    `patients_unsupported`, the same of the patients' file.
+    `patients_unsupported`, the same of the patients' file.  `direction`: as `search_donors`, the same on every rank: every
+    rank's DonorSearch is opened with it, so the lists rank 0 merges are of one direction.
 
     `compute(config, patient_lines, donor_lines, first) -> (hits, n_hits, stats)` can be injected (tests): a rank then folds
-    its chunks' lists, and rank 0 the ranks' lists, with grim.search.merge_hit_lists.  Every wait ends `timeout_s` seconds
+    its chunks' lists, and rank 0 the ranks' lists, with grim.search.merge_hit_lists (the direction is then the one `compute`
+    folds under; the keyword is only checked).  Every wait ends `timeout_s` seconds
     after the call began at the latest, or when a peer reports an error; every rank raises when any rank failed."""
+    from .match import direction_code
     from .search import _check
 
     top_n, min_p0 = _check(top_n, min_p0)
     return _search_sharded(_Job("search_sharded", timeout_s, chunk_lines), conf_file, patients_path, keep_loci, top_n, min_p0, graph,
-                           compute, block_lines)
+                           compute, block_lines, direction_code(direction))
 
 
-def _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, compute, block_lines):
-    """search_sharded as `job`, top_n and min_p0 checked"""
+def _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, compute, block_lines, direction=0):
+    """search_sharded as `job`, top_n, min_p0 and direction checked"""
     import numpy as np
 
     from .blocks import read_lines
@@ -814,7 +817,7 @@ def _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, gra
             from .search import DonorSearch
 
             imp = job.imputation(config, graph)
-            search = DonorSearch(imp, plines, config, keep_loci, top_n, min_p0, block_lines)
+            search = DonorSearch(imp, plines, config, keep_loci, top_n, min_p0, block_lines, direction=direction)
             job.cleanup.callback(search.close)
             patients_bad = list(imp.unsupported)
         else:
@@ -869,21 +872,23 @@ def _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, gra
 
 
 def search_file_sharded(conf_file, patients_path, keep_loci, out_path, top_n, min_p0=0.0, chunk_lines=None, graph=None, timeout_s=1800,
-                        block_lines=65536):
+                        block_lines=65536, direction="either"):
     """grim.search.search_file across the ranks of the job through `search_sharded`: rank 0 writes the CSV at `out_path`, byte
     for byte the file `search_file` writes; every rank returns when it is written, and every rank raises when rank 0 could
-    not write it.  -> stats, the same on every rank"""
+    not write it.  `direction`: as `search_sharded`.  -> stats, the same on every rank"""
     from .blocks import read_lines
+    from .match import direction_code
     from .imputation.networkx_graph import Graph
     from .run_impute_def import load_config
     from .search import _check, write_hits_csv
 
     top_n, min_p0 = _check(top_n, min_p0)
+    direction = direction_code(direction)
     config, _ = load_config(conf_file)
     if graph is None:  # (the CSV's rows need it too)
         graph = Graph(config).build_graph(config["node_file"], config["top_links_file"], config["edges_file"])
     job = _Job("search_sharded", timeout_s, chunk_lines)
-    ok, hits, n_hits, stats = _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, None, block_lines)
+    ok, hits, n_hits, stats = _search_sharded(job, conf_file, patients_path, keep_loci, top_n, min_p0, graph, None, block_lines, direction)
     failure = []
 
     def write():  # on rank 0 (or alone) -> what the other ranks learn: "ok" or the error's text

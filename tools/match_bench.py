@@ -4,11 +4,15 @@ the pop4 graph, 100 000 mixed subjects of seed 3, MR priors; the first 8 and the
 JSON line with medians over --steps steps after --warmup:
 
   (a) impute_kernel_ms   the donors' batch's kernels, grim_batch_kernel_ms(GRIM_MS_TOTAL) in timing mode
-  (b) match_kernel_ms    grim_match_kernel_ms of the run on that batch, per patient count
+  (b) match_kernel_ms    grim_match_kernel_ms of the run on that batch, per patient count; with --direction / --graded one
+                         leg per (direction, graded) in the same run, `legs`, the first leg being the one to compare with
+                         (the default leg, either and ungraded, is the kernel every caller had before), and
+                         `download_bytes`, the size of a leg's result records
   (c) text_route_s       what a caller had before: match_umug_text on the printed .umug of the patients and of the first
                          --text-donors donors, wall time, scaled to all donors (the fold is linear in the donors)
 
     python tools/match_bench.py [--subjects N] [--steps K] [--warmup W] [--keep A,B,C,DQB1,DRB1] [--patients 8,64]
+                                [--direction either,gvh] [--graded off|on|both]
 """
 import argparse
 import json
@@ -32,6 +36,8 @@ def main():
     ap.add_argument("--keep", default="A,B,C,DQB1,DRB1", help="locus names to keep, comma separated")
     ap.add_argument("--patients", default="8,64", help="patient counts, comma separated: the first N subjects")
     ap.add_argument("--text-donors", type=int, default=1000, help="donors of the text route (scaled to --subjects)")
+    ap.add_argument("--direction", default="either", help="mismatch directions (either, gvh, hvg), comma separated")
+    ap.add_argument("--graded", default="off", choices=["off", "on", "both"], help="ungraded records, graded ones, or a leg each")
     args = ap.parse_args()
 
     import __graft_entry__ as ge
@@ -40,7 +46,7 @@ def main():
     from grim.imputation.impute import Imputation
     from grim.imputation.networkx_graph import Graph
     from grim.marginal import keep_mask
-    from grim.match import match_umug_text
+    from grim.match import direction_code, match_umug_text
     from grim.run_impute_def import load_config
 
     pops = harness.POPS["pop4"]
@@ -69,9 +75,14 @@ def main():
     priors = nat.prior_matrices(ps, pops, parsed.races())
     batch = nat.DeviceBatch(ctx, g.device(ctx), params, parsed.subjects(), parsed.tokens(), priors)
     batch.set_timing(True)
-    matcher = nat.Matcher(ctx, mask, [g.adict.count(s) for s in range(len(g.full_loci))])
-    a_ms, b_ms, stats = [], {n: [] for n in counts}, {}
+    legs = [(d, gr) for gr in {"off": [False], "on": [True], "both": [False, True]}[args.graded]
+            for d in [x for x in args.direction.split(",") if x]]
+    n_alleles = [g.adict.count(s) for s in range(len(g.full_loci))]
+    matchers = []
+    a_ms, b_ms, stats = [], {leg: {n: [] for n in counts} for leg in legs}, {}
     try:
+        for d, gr in legs:
+            matchers.append(nat.Matcher(ctx, mask, n_alleles, direction_code(d), gr))
         batch.run()
         res, rows = batch.results()
         for step in range(args.warmup + args.steps):
@@ -79,13 +90,16 @@ def main():
             if step >= args.warmup:
                 a_ms.append(batch.kernel_ms(nat.MS_TOTAL))
             for n in counts:  # the first n device subjects, their rows where the batch has them
-                matcher.set_patients(res[:n], rows)
-                matcher.run(batch)
-                if step >= args.warmup:
-                    b_ms[n].append(matcher.kernel_ms())
-                stats[n] = matcher.stats()
+                for leg, matcher in zip(legs, matchers):  # the legs in turn within a step: drift hits them alike
+                    matcher.set_patients(res[:n], rows)
+                    matcher.run(batch)
+                    if step >= args.warmup:
+                        b_ms[leg][n].append(matcher.kernel_ms())
+                    if leg == legs[0]:
+                        stats[n] = matcher.stats()
     finally:
-        matcher.close()
+        for matcher in matchers:
+            matcher.close()
         batch.close()
         parsed.close()
     c_s = None
@@ -106,7 +120,12 @@ def main():
         "workload": "pop4 graph, %d mixed subjects (seed 3) as donors, MR priors, keep %s" % (args.subjects, "~".join(keep)),
         "steps": args.steps, "warmup": args.warmup,
         "impute_kernel_ms": statistics.median(a_ms),
-        "match_kernel_ms": {str(n): statistics.median(v) for n, v in b_ms.items()},
+        "match_kernel_ms": {str(n): statistics.median(v) for n, v in b_ms[legs[0]].items()},
+        "legs": {"%s%s" % (d, "~graded" if gr else ""): {
+            "match_kernel_ms": {str(n): statistics.median(v) for n, v in b_ms[(d, gr)].items()},
+            "min_ms": {str(n): min(v) for n, v in b_ms[(d, gr)].items()},
+            "download_bytes": {str(n): n * len(res) * (nat.MATCH_GRADE_DT if gr else nat.MATCH_DT).itemsize for n in counts}}
+            for d, gr in legs},
         "text_route_s_scaled": {str(n): v for n, v in c_s.items()} if c_s else None, "text_donors": args.text_donors,
         "match_stats": {str(n): s for n, s in stats.items()},
     }))
