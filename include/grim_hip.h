@@ -652,7 +652,7 @@ int grim_match_stats(const grim_match *m, uint64_t out[8]);
 double grim_match_kernel_ms(const grim_match *m);
 void grim_match_free(grim_match *m);
 
-/* Mismatch direction and per-locus grades (csrc/grim_match_grade.h).  Everything of the block above holds -- the flags, the
+/* Mismatch direction and per-locus grades (csrc/grim_match.h).  Everything of the block above holds -- the flags, the
  * weights, patient-major results, the donor-row outer fold, the patient-row inner fold, +0.0 starts, no fma, the statistics --
  * except the per-slot mismatch function and, when graded, the record.  With x1, x2 the patient's fields of a slot, y1, y2 the
  * donor's and eq(x, y) = x == y and x != 0:

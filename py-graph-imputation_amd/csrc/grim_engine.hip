@@ -25,7 +25,6 @@
 #include "grim_refresh.h"
 #include "grim_marginal.h"
 #include "grim_match.h"
-#include "grim_match_grade.h"
 #include "grim_search.h"
 #include "grim_groups.h"
 #include "grim_engine_internal.h"
@@ -2887,7 +2886,7 @@ struct grim_match {
 };
 
 static_assert(MT_DIR_EITHER == GRIM_MATCH_DIR_EITHER && MT_DIR_GVH == GRIM_MATCH_DIR_GVH && MT_DIR_HVG == GRIM_MATCH_DIR_HVG,
-              "the directions of grim_match_grade.h and of grim_hip.h have drifted apart");
+              "the directions of grim_match.h and of grim_hip.h have drifted apart");
 static_assert(sizeof(grim_match_rec) == 8 * MT_REC && sizeof(grim_match_grade_rec) == 8 * MT_GRADE_REC,
               "the match records and the kernels' bin counts have drifted apart");
 
@@ -3012,25 +3011,17 @@ extern "C" int grim_match_set_groups(grim_match *m, const grim_groups *g) {
   return m->gp.attach(c, "grim_match_set_groups", g);
 }
 
-// the pair kernel of the matcher's direction and record: (either, ungraded) is mt_pair_kernel itself
+// the pair kernel's six instances, at direction * 2 + graded (grim_match_create_ex refuses a direction above _HVG)
 template <int DIR, bool GRADED>
-static void mt_launch_dir(hipStream_t st, const MtSide &P, uint32_t n_p, uint32_t p0, uint32_t np, const MtSide &D, uint32_t n,
-                          uint32_t keep_mask, double *out, unsigned long long *stat) {
-  hipLaunchKernelGGL((mt_pair_dir_kernel<DIR, GRADED>), dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, keep_mask, out, stat);
+static void mt_launch(hipStream_t st, const MtSide &P, uint32_t n_p, uint32_t p0, uint32_t np, const MtSide &D, uint32_t n,
+                      uint32_t keep_mask, double *out, unsigned long long *stat) {
+  hipLaunchKernelGGL((mt_pair_kernel<DIR, GRADED>), dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, keep_mask, out, stat);
 }
-
-static void mt_launch(const grim_match *m, hipStream_t st, const MtSide &P, uint32_t n_p, uint32_t p0, uint32_t np, const MtSide &D,
-                      uint32_t n, double *out, unsigned long long *stat) {
-  const uint32_t k = m->keep_mask;
-  switch (m->direction * 2u + (m->graded ? 1u : 0u)) {
-    case 0: hipLaunchKernelGGL(mt_pair_kernel, dim3(n, np), dim3(64), 0, st, P, n_p, p0, D, n, k, out, stat); break;
-    case 1: mt_launch_dir<MT_DIR_EITHER, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
-    case 2: mt_launch_dir<MT_DIR_GVH, false>(st, P, n_p, p0, np, D, n, k, out, stat); break;
-    case 3: mt_launch_dir<MT_DIR_GVH, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
-    case 4: mt_launch_dir<MT_DIR_HVG, false>(st, P, n_p, p0, np, D, n, k, out, stat); break;
-    default: mt_launch_dir<MT_DIR_HVG, true>(st, P, n_p, p0, np, D, n, k, out, stat); break;
-  }
-}
+static constexpr decltype(&mt_launch<MT_DIR_EITHER, false>) MT_LAUNCH[] = {
+    mt_launch<MT_DIR_EITHER, false>, mt_launch<MT_DIR_EITHER, true>, mt_launch<MT_DIR_GVH, false>,
+    mt_launch<MT_DIR_GVH, true>,     mt_launch<MT_DIR_HVG, false>,   mt_launch<MT_DIR_HVG, true>};
+static_assert(sizeof(MT_LAUNCH) / sizeof(MT_LAUNCH[0]) == 2 * (GRIM_MATCH_DIR_HVG + 1),
+              "one instance for every direction grim_match_create_ex lets in, ungraded and graded");
 
 static uint32_t mt_rec_doubles(const grim_match *m) { return m->graded ? MT_GRADE_REC : MT_REC; }
 
@@ -3052,8 +3043,9 @@ static int mt_run(grim_match *m, const char *who, const grim_subject_result *res
   if (pairs) {
     HIPCHK(hipMemsetAsync(m->d_out, 0, sizeof(double) * rec * pairs, st), c, -1);  // a pair that is not computed reads as zero bytes
     const MtSide P = m->P.side(), D = m->D.side();
+    const auto launch = MT_LAUNCH[m->direction * 2u + (m->graded ? 1u : 0u)];
     for_slabs(n_p, [&](uint32_t p0, uint32_t np) {
-      mt_launch(m, st, P, n_p, p0, np, D, n, m->d_out, m->d_stat);
+      launch(st, P, n_p, p0, np, D, n, m->keep_mask, m->d_out, m->d_stat);
     });
     HIPCHK(hipGetLastError(), c, -1);
   }

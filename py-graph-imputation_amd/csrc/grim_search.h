@@ -1,5 +1,5 @@
 // grim_search.h -- donor search: each patient's best N donors by match probability, selected on the device (gfx950, wave64)
-// from the records mt_pair_kernel leaves in the matcher's result buffer (include/grim_hip.h, grim_search_*).
+// from the ungraded records mt_pair_kernel<DIR, false> leaves in the matcher's result buffer (include/grim_hip.h, grim_search_*).
 //
 // Contract.  Input: the inputs of grim_match.h (keep mask K, n_alleles, patients set once, donors in any number of runs), and
 //   top_n   in 1..GRIM_SEARCH_MAX_N

@@ -158,6 +158,11 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _per_slot(counts):
+    """per-slot counts (n_alleles, n_groups), padded with 0 to MAXL -> the uint32[GRIM_MAXL] a create call takes"""
+    return (C.c_uint32 * MAXL)(*([int(x) for x in counts] + [0] * (MAXL - len(counts))))
+
+
 def _records(res, rows):
     """host records -> (res RESULT_DT[n], rows ROW_DT[m], the four C arguments res, n, rows, m); the caller keeps the arrays
     alive across the call"""
@@ -428,8 +433,7 @@ class EmAccumulator(_Handle):
     def __init__(self, ctx, n_alleles, n_pops, first_capacity=1 << 20):
         L = _em_lib()
         self.ctx = ctx
-        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
-        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        arr = _per_slot(n_alleles)
         self.h = L.grim_em_create(ctx.h, arr, int(n_pops), int(first_capacity))
         if not self.h:
             raise NativeError("grim_em_create failed: " + ctx.error())
@@ -539,13 +543,12 @@ class Groups(_Handle):
     def __init__(self, ctx, table, n_alleles, n_groups):
         L = _groups_lib()
         self.ctx = ctx
-        na = [int(x) for x in n_alleles] + [0] * (MAXL - len(n_alleles))
-        ng = [int(x) for x in n_groups] + [0] * (MAXL - len(n_groups))
+        na, ng = _per_slot(n_alleles), _per_slot(n_groups)
         table = np.ascontiguousarray(table, dtype=np.uint16)
         need = sum(min(x, 4095) + 1 for x in na)  # the library reads no table before it has checked the sizes
         if table.ndim != 1 or len(table) < need:
             raise ValueError("the table holds %d entries, the slots need %d" % (table.size, need))
-        self.h = L.grim_groups_create(ctx.h, _ptr(table), (C.c_uint32 * MAXL)(*na), (C.c_uint32 * MAXL)(*ng))
+        self.h = L.grim_groups_create(ctx.h, _ptr(table), na, ng)
         if not self.h:
             raise NativeError("grim_groups_create failed: " + ctx.error())
 
@@ -732,8 +735,7 @@ class Matcher(_Handle):
     def __init__(self, ctx, keep_mask, n_alleles, direction=0, graded=False):
         L = _match_lib()
         self.ctx = ctx
-        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
-        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        arr = _per_slot(n_alleles)
         direction = int(direction)
         if not 0 <= direction < 1 << 32:
             raise ValueError("direction out of range")
@@ -771,23 +773,21 @@ class Matcher(_Handle):
     def donors(self):
         return int(_match_lib().grim_match_donors(self.h))
 
+    def _results(self, name, dtype):
+        n_p, n_d = self.patients(), self.donors()
+        out = np.zeros((n_p, n_d), dtype=dtype)
+        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
+        self._check(getattr(_match_lib(), name)(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
+                                                _ptr(df) if n_d else None), name, code=False)
+        return out, pf, df
+
     def results(self):
         """-> (records MATCH_DT[patients][donors], patient flags u8[patients], donor flags u8[donors])"""
-        n_p, n_d = self.patients(), self.donors()
-        out = np.zeros((n_p, n_d), dtype=MATCH_DT)
-        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
-        self._check(_match_lib().grim_match_results(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
-                                                    _ptr(df) if n_d else None), "grim_match_results", code=False)
-        return out, pf, df
+        return self._results("grim_match_results", MATCH_DT)
 
     def results_graded(self):
         """of a graded matcher -> (records MATCH_GRADE_DT[patients][donors], patient flags, donor flags)"""
-        n_p, n_d = self.patients(), self.donors()
-        out = np.zeros((n_p, n_d), dtype=MATCH_GRADE_DT)
-        pf, df = np.zeros(n_p, dtype=np.uint8), np.zeros(n_d, dtype=np.uint8)
-        self._check(_match_lib().grim_match_results_graded(self.h, _ptr(out) if out.size else None, _ptr(pf) if n_p else None,
-                                                           _ptr(df) if n_d else None), "grim_match_results_graded", code=False)
-        return out, pf, df
+        return self._results("grim_match_results_graded", MATCH_GRADE_DT)
 
     def stats(self):
         out = (C.c_uint64 * 8)()
@@ -863,8 +863,7 @@ class Searcher(_Handle):
     def __init__(self, ctx, keep_mask, n_alleles, top_n, min_p0=0.0, direction=0):
         L = _search_lib()
         self.ctx = ctx
-        counts = list(n_alleles) + [0] * (MAXL - len(n_alleles))
-        arr = (C.c_uint32 * MAXL)(*[int(x) for x in counts])
+        arr = _per_slot(n_alleles)
         top_n = int(top_n)
         if not 0 <= top_n < 1 << 32:
             raise ValueError("top_n out of range")

@@ -422,7 +422,7 @@ def match_probabilities(imputation, patient_lines, donor_lines_or_path, config, 
     `imputation.on_unsupported` as in `impute_lines_block`.  `groups`: an AlleleGroups of the imputation's graph or a group
     specification (grim.groups): alleles are equal when their groups are -- on the device by group id, in the pairs folded
     here by group name -- and the result equals `match_umug_text` on the regrouped text.  `direction`, `graded`: as
-    `match_records`, on the device (csrc/grim_match_grade.h) and in the pairs folded here; graded, records is
+    `match_records`, on the device (csrc/grim_match.h) and in the pairs folded here; graded, records is
     nat.MATCH_GRADE_DT."""
     pairing = _Pairing(imputation, patient_lines, donor_lines_or_path, config, keep_loci, block_lines, planb, em, groups, direction,
                        graded)

@@ -1,4 +1,4 @@
-"""Mismatch direction and per-locus grades on the device (csrc/grim_match_grade.h through grim/match.py and grim/search.py,
+"""Mismatch direction and per-locus grades on the device (csrc/grim_match.h through grim/match.py and grim/search.py,
 DESIGN 4.12): the smallest shapes at which the pair kernel can go wrong, through the host-records door against the record
 twin, bit for bit; what the directions and the graded record owe each other; reuse; refusals; a group map; the search; one
 golden end to end against the text twin."""
@@ -193,7 +193,7 @@ def test_the_shapes_are_not_vacuous(shapes, mask):
 @pytest.mark.parametrize("mask", MASKS, ids=[bin(m) for m in MASKS])
 def test_what_the_device_results_owe_each_other(ctx, shapes, mask):
     """on the device's own records: the directed mm[0] is never below either's, exactly; graded records hold the ungraded
-    bytes.  (either, ungraded) is the matcher every caller had before: mt_pair_kernel itself."""
+    bytes.  (either, ungraded) is the matcher grim_match_create makes: one of the six instances of mt_pair_kernel."""
     either = _device(ctx, shapes, mask, "either", False)[0]
     _same(_device(ctx, shapes, mask, "either", False), _twin(shapes, mask, "either", False))
     for direction in ("either", "gvh", "hvg"):
